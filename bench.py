@@ -21,6 +21,15 @@ Timing: W warm-up steps, barrier + device sync, K timed steps, barrier + device 
 ranks is reported.  Inputs are resident in HBM before the timed region.  Per-kernel durations come
 from HIP events recorded around every 64th launch of each kernel class on the library's stream
 inside the timed region.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs,
+the JSON line (its roofline fields come from the events already recorded inside the timed region).
+--full adds what takes runs of its own after the timed region: the copy calibration, the cold FD Jv
+alone (jv_alone), the CPU baseline with its thread probe and the CPU/GPU agreement check.
+
+--dump-outputs DIR writes what the last timed step handed its caller -- u, res = F(u) and the
+step's statistics -- as DIR/<name>.npy (float64; a fixed seeded sample of a vector above 2^21 elements).
+The inputs are functions of the arguments alone, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -112,7 +121,14 @@ def parse():
                     help="time every k-th launch of each kernel class (HIP events; k > 1 keeps their cost out of "
                          "the timed region); 0 = 64 for bratu2d (~6000 launches per class), 8 for the heat "
                          "workloads (11 matvecs per step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the measurements that take runs of their own: copy "
+                         "calibration, the FD Jv alone, the CPU baseline (thread probe included) and the CPU/GPU "
+                         "agreement check; without it those fields of the line are null")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (u, res, stats) as DIR/<name>.npy, float64; "
+                         "vectors above 2^21 elements as a fixed seeded sample (<name>_rank<r>.npy with N > 1 ranks)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and agreement")
     ap.add_argument("--transport", choices=["rccl", "mailbox"], default="rccl",
                     help="N > 1: rccl = nk_dist_init (RCCL bootstrap; peer mailbox + IPC ghost planes when available); "
                          "mailbox = IPC handles over gloo, no RCCL (diagnostic: lets ranks share one GPU -- with "
@@ -226,6 +242,23 @@ def copy_calibration(device, n=1 << 27, reps=5):
     if us <= 0:
         return None
     return 16.0 * n / (us * 1e-6) / 1e9
+
+
+DUMP_ELEMS = 1 << 21  # per dumped array over all ranks: 16 MB of float64 (u and res: 32 MB at most)
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: every array as dirname/<name>.npy (<name>_rank<r>.npy with more than one rank), flat
+    float64.  An array above this rank's share of DUMP_ELEMS is written as a sample at sorted indices
+    drawn with a fixed seed from its size alone, so two runs with the same arguments sample the same
+    elements."""
+    os.makedirs(dirname, exist_ok=True)
+    cap = max(1, DUMP_ELEMS // world)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0).integers(0, a.size, cap))]
+        np.save(os.path.join(dirname, name + ("" if world == 1 else f"_rank{rank}") + ".npy"), a)
 
 
 def free_port() -> int:
@@ -622,6 +655,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     if args.workload == "bratu2d" and not args.memory:
@@ -777,10 +812,16 @@ def main():
     if dist is not None:
         paths = [None] * world
         dist.all_gather_object(paths, path)
-    if rank == 0:
+    if args.dump_outputs:  # what the last timed step handed its caller: u, res = F(u) and its statistics
+        st = last.stats
+        dump_outputs(args.dump_outputs,
+                     {"u": W.u.to_numpy(), "res": W.res.to_numpy(),
+                      "stats": np.array([st.outer_iterations, st.inner_iterations, st.n_res, last.n_matvec], float)},
+                     rank, world)
+    if rank == 0 and args.full:
         log("timed steps done; copy calibration")
-    copy_gbs = copy_calibration(device) if rank == 0 else None
-    jv_alone = jv_alone_calibration(W, ctx) if (rank == 0 and world == 1 and args.workload == "bratu2d"
+    copy_gbs = copy_calibration(device) if (rank == 0 and args.full) else None
+    jv_alone = jv_alone_calibration(W, ctx) if (rank == 0 and args.full and world == 1 and args.workload == "bratu2d"
                                                   and args.jv == "fd" and not args.no_prof) else None
 
     # Two byte counts per kernel class (nk_prof_entry): `bytes` = the operand bytes the kernel moves
@@ -914,7 +955,7 @@ def main():
                                   block_of=args.block_of))
         if args.block_of:
             out["ranks"] = paths  # the rig's path report: faces exchanged, BLK instances, peer waits
-        if world == 1 and not args.no_cpu_baseline and not args.global_n:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.global_n:
             # the node's host cores: the fastest thread count the process's affinity mask offers (the
             # headline figure), and the per-GPU share the box gives one GPU (OMP_NUM_THREADS, 16 there)
             # beside it; nproc is the machine's full count

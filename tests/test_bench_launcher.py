@@ -171,6 +171,60 @@ def test_pgrid_factorisation():
         b.pgrid_of("2,2,1", 8)
 
 
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: small arrays whole, large ones as the same seeded sample on every call (two builds
+    are compared element for element), flat float64, every rank's share within the size bound."""
+    import numpy as np
+
+    b = _bench_module()
+    rng = np.random.default_rng(7)
+    big = rng.standard_normal((3, b.DUMP_ELEMS // 2 + 5))  # 1.5 x the bound: sampled
+    small = np.arange(12.0).reshape(3, 4)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"u": big, "stats": small})
+    ua, ub = np.load(tmp_path / "a" / "u.npy"), np.load(tmp_path / "b" / "u.npy")
+    assert ua.dtype == np.float64 and ua.shape == (b.DUMP_ELEMS,) and np.array_equal(ua, ub)
+    assert np.isin(ua, big).all() and len(np.unique(ua)) > b.DUMP_ELEMS // 2  # elements of u, spread over it
+    assert np.array_equal(np.load(tmp_path / "a" / "stats.npy"), small.ravel())
+    b.dump_outputs(str(tmp_path / "r"), {"u": big}, rank=1, world=2)  # N ranks share the bound
+    assert np.load(tmp_path / "r" / "u_rank1.npy").shape == (b.DUMP_ELEMS // 2,)
+    assert 2 * 8 * b.DUMP_ELEMS <= 64 << 20  # u and res of one run
+
+
+def test_steps_must_be_positive():
+    p = run(["--gpus", "1", "--steps", "0", "--launch-probe", "0"])
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` (a small Bratu grid) times exactly --steps steps, carries ms_per_step, runs
+    none of the --full measurements (their fields are null) and with --dump-outputs writes the u, res and
+    statistics of its last timed step: the same bits on a second run, ||res|| the line's newton_n_res."""
+    import numpy as np
+
+    args = ["--gpus", "1", "--side", "200", "--steps", "2", "--warmup", "1", "--itmax", "60"]
+    lines = []
+    for d in ("a", "b"):
+        p = run(args + ["--dump-outputs", str(tmp_path / d)], timeout=120)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert "cpu baseline" not in p.stderr and "copy calibration" not in p.stderr
+        lines.append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')][-1]))
+    line = lines[0]
+    mv = line["config"]["matvecs_per_step"]  # 60 Arnoldi steps + the restart residual
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and mv == 61
+    assert line["value"] == pytest.approx(mv * 1e3 / line["ms_per_step"], rel=1e-3)
+    assert line["cpu_baseline"] is None and line["jv_alone"] is None and line["calibration"]["copy_gbs"] is None
+    assert "cpu_gpu_agreement" not in line
+    u, res, st = (np.load(tmp_path / "a" / f"{k}.npy") for k in ("u", "res", "stats"))
+    assert u.dtype == res.dtype == np.float64 and u.shape == res.shape == (200 * 200,)
+    assert st.tolist() == [1.0, 60.0, line["newton_n_res"], float(mv)]
+    assert np.linalg.norm(res) == pytest.approx(line["newton_n_res"], rel=1e-12)
+    for k in ("u", "res", "stats"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")), k
+    assert lines[1]["newton_n_res"] == line["newton_n_res"]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("fail", ["1", "rank:1"])
 def test_rccl_bootstrap_failure_falls_back_to_the_mailbox(fail):

@@ -12,7 +12,7 @@ tail -n 2 "$OUT/gputest.log"
 echo "[check] smoke"
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 echo "[check] bench"
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > "$OUT/bench_driver_style.log" 2>&1
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 > "$OUT/bench_driver_style.log" 2>&1
 tail -n 1 "$OUT/bench_driver_style.log" > "$OUT/bench_driver_style.json"
 python3 -c "import json; d=json.load(open('$OUT/bench_driver_style.json')); print(d['value'], d['roofline']['frac'])"
 echo "[check] done"

@@ -64,7 +64,7 @@ echo "[profile] bench lines"
 for w in $TAGS; do
     TJ="$DST/pmc_traffic_${WFILE[$w]}.json"
     [ -f "$TJ" ] || TJ="profiles/$R/pmc_traffic_${WFILE[$w]}.json"  # PMC passes of an earlier call
-    timeout -k 10 300 python3 bench.py ${WARGS[$w]} --traffic-json "$TJ" \
+    timeout -k 10 300 python3 bench.py ${WARGS[$w]} --full --traffic-json "$TJ" \
         > "$OUT/bench_$w.log" 2>&1
     tail -n 1 "$OUT/bench_$w.log" > "$DST/bench_$w.json"
 done
