@@ -74,6 +74,9 @@ extern "C" {
 #define NK_PRECOND_ILU0 4  /* z = (L U)^-1 v: ILU(0) of J in natural order, the `ilu(collect(J))` of examples/bratu.jl:
                               119-137 on J's own pattern (exact LU for the 1D tridiagonal J); diag = D~ from
                               nk_ilu0_factor.  Distributed: block Jacobi (each slab factored on its own) */
+#define NK_PRECOND_MG 5    /* z = one geometric multigrid V-cycle on v, from x = 0 (a fixed linear map: valid for
+                              NK_ALGO_GMRES as well as NK_ALGO_FGMRES); data = the nk_mg handle (nk_mg_create).
+                              Built-in stencil kinds, bc_zero!, one rank */
 typedef int (*nk_user_precond)(void* data, struct nk_ctx* ctx, double* out, const double* in);
 typedef struct nk_precond {
     int32_t kind;          /* NK_PRECOND_*                                   */
@@ -242,6 +245,39 @@ typedef struct nk_krylov_stats {
  * GMRES preconditioner solves with; unused otherwise).  Synchronises. */
 int nk_precond_apply(nk_ctx* ctx, const nk_problem* p, const nk_precond* N, const double* u, const double* F0,
                      int32_t jv_mode, double* z, const double* v);
+
+/* ---------------------------------------------------------------- geometric multigrid (NK_PRECOND_MG)
+ * One V-cycle for the stencil Jacobians A_0 = Σ_a k_a δ²_a(h_a) + diag(s) (Bratu: k = 1, s = λ exp(u);
+ * heat: k = θ a Δt, s = -1 with θ = 1 / (1 - α) / ½ for Euler / Midpoint / Trapezoid).  Per axis
+ * n_{l+1} = n_l / 2 while n_l > 3; coarse operators are rediscretised (h_l = L / (n_l + 1), s_{l+1} = R s_l);
+ * linear prolongation P on the non-nested grids, restriction R = D^-1 P^T as a gather; weighted Jacobi
+ * smoothing (nu pre / post sweeps, coarse_sweeps on the coarsest level, every level from x = 0).  The
+ * hierarchy is allocated by nk_mg_create; nk_mg_apply only enqueues kernels on the context's stream (no
+ * host synchronisation, no allocation, no atomics).  DESIGN.md §10. */
+typedef struct nk_mg nk_mg;
+typedef struct nk_mg_opts {
+    int32_t nu;             /* pre- and post-smoothing sweeps (0: the default 2)            */
+    int32_t coarse_sweeps;  /* sweeps on the coarsest level (0: the default 8)              */
+    double omega;           /* Jacobi weight (0: the default 2 d / (2 d + 1), d = axes)     */
+    int32_t max_levels;     /* 0: coarsen until every axis is <= 3                          */
+} nk_mg_opts;
+/* the level extents of a grid (host only, no GPU): extents[3 l + a] = n_a of level l (1 for unused axes),
+ * at most cap levels written, *nlevels = the number of levels */
+int nk_mg_plan(const int64_t n[3], int32_t max_levels, int64_t* extents, int32_t cap, int32_t* nlevels);
+/* opts may be null (the defaults).  NK_E_ARG for periodic boundaries, a distributed context, NK_USER* kinds */
+int nk_mg_create(nk_ctx* ctx, const nk_problem* p, const nk_mg_opts* opts, nk_mg** out);
+int nk_mg_destroy(nk_mg* mg);
+/* levels in use: nk_mg_plan's count, fewer when set-up truncated the hierarchy before a level whose
+ * diagonal changes sign or vanishes */
+int nk_mg_levels(nk_mg* mg, int32_t* nlevels);
+/* k and s of J(u) from the problem's kind; the level-0 diagonal is nk_jacobian_diag's.  Synchronises. */
+int nk_mg_set_jacobian(nk_mg* mg, const nk_problem* p, const double* u);
+/* caller-supplied coefficients: k per axis, s = s_dev (device, n doubles) or the constant s_const when null.
+ * nk_newton_krylov refreshes a hierarchy from each step's u (nk_mg_set_jacobian) -- except one whose operator was
+ * set here: that stays the caller's until nk_mg_set_jacobian is called on it again */
+int nk_mg_set_operator(nk_mg* mg, const double k[3], const double* s_dev, double s_const);
+/* z = V-cycle(v) */
+int nk_mg_apply(nk_mg* mg, double* z, const double* v);
 
 /* memory = Krylov workspace memory (GMRES restart length; default 20 like Krylov.jl). */
 int nk_workspace_create(nk_ctx* ctx, int32_t algo, const nk_problem* p, int32_t memory, nk_workspace** out);

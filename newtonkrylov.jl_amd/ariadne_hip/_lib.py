@@ -30,6 +30,7 @@ NK_BC_ZERO, NK_BC_PERIODIC = 0, 1
 NK_JV_EXACT, NK_JV_FD = 0, 1
 NK_ALGO_GMRES, NK_ALGO_CG, NK_ALGO_FGMRES = 0, 1, 2
 NK_PRECOND_NONE, NK_PRECOND_DIAG, NK_PRECOND_USER, NK_PRECOND_GMRES, NK_PRECOND_ILU0 = 0, 1, 2, 3, 4
+NK_PRECOND_MG = 5
 
 _ERRORS = {-1: "HIP error", -2: "invalid argument", -3: "out of device memory", -4: "RCCL error", -5: "bad state", -6: "user callback failed"}
 
@@ -57,6 +58,10 @@ NK_USER_PRECOND = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_v
 class nk_precond(C.Structure):
     _fields_ = [("kind", C.c_int32), ("diag", C.c_void_p), ("apply", NK_USER_PRECOND), ("data", C.c_void_p),
                 ("inner", C.c_void_p), ("itmax", C.c_int32)]
+
+
+class nk_mg_opts(C.Structure):
+    _fields_ = [("nu", C.c_int32), ("coarse_sweeps", C.c_int32), ("omega", C.c_double), ("max_levels", C.c_int32)]
 
 
 class nk_user_ops(C.Structure):
@@ -130,6 +135,13 @@ SIGNATURES = {
     "nk_jacobian_diag": (C.c_int, [_VP, _PP, _VP, _VP, _I32]),
     "nk_ilu0_factor": (C.c_int, [_VP, _PP, _VP, _VP]),
     "nk_precond_apply": (C.c_int, [_VP, _PP, _VP, _VP, _VP, _I32, _VP, _VP]),
+    "nk_mg_plan": (C.c_int, [C.POINTER(_I64), _I32, C.POINTER(_I64), _I32, C.POINTER(_I32)]),
+    "nk_mg_create": (C.c_int, [_VP, _PP, C.POINTER(nk_mg_opts), C.POINTER(_VP)]),
+    "nk_mg_destroy": (C.c_int, [_VP]),
+    "nk_mg_levels": (C.c_int, [_VP, C.POINTER(_I32)]),
+    "nk_mg_set_jacobian": (C.c_int, [_VP, _PP, _VP]),
+    "nk_mg_set_operator": (C.c_int, [_VP, _PD, _VP, _D]),
+    "nk_mg_apply": (C.c_int, [_VP, _VP, _VP]),
     "nk_dot": (C.c_int, [_VP, _I64, _VP, _VP, _PD]),
     "nk_mgs_step": (C.c_int, [_VP, _I64, C.POINTER(_VP), _I32, _VP, _I32, _PD]),
     "nk_norm": (C.c_int, [_VP, _I64, _VP, _PD]),

@@ -230,6 +230,17 @@ class Result(NamedTuple):
     n_matvec: int = 0
 
 
+def _refreshed(P, J):
+    """A preconditioner object given for the whole Newton solve: one that follows the Jacobian (the multigrid
+    V-cycle, as nk_newton_krylov does) is refreshed from this step's u -- unless its operator is the caller's
+    (from_coefficients); the others are used as they are."""
+    from .precond import MultigridPreconditioner
+
+    if isinstance(P, MultigridPreconditioner) and not P.caller_operator:
+        return P.update(J)
+    return P
+
+
 def newton_krylov_(F_: DeviceResidual, u: DeviceArray, p=None, res: DeviceArray | None = None, *,
                    tol_rel: float = 1.0e-6, tol_abs: float = 1.0e-12, max_niter: int = 50,
                    forcing: Forcing | None = EisenstatWalker(), verbose: int = 0, algo: str = "gmres",
@@ -238,15 +249,20 @@ def newton_krylov_(F_: DeviceResidual, u: DeviceArray, p=None, res: DeviceArray 
     """newton_krylov!(F!, u, p, res; kwargs...) -- src/Ariadne.jl:288-372 (and the 3-arg form :259-263).
 
     `N` (right) and `M` (left preconditioner) are preconditioner objects or factories `N(J)` /
-    `M(J)` called per Newton step (ariadne_hip.precond: `jacobi`, `ilu0`, `gmres_preconditioner`,
+    `M(J)` called per Newton step (ariadne_hip.precond: `jacobi`, `ilu0`, `multigrid`, `gmres_preconditioner`,
     DiagonalPreconditioner, UserPreconditioner), forwarded as Krylov.jl's `N` / `M` (:323-329);
     an `N` or `M` inside krylov_kwargs wins over the factory, as the reference's kwarg merge does.
     Additions of the HIP path: `memory` (Krylov workspace memory = GMRES restart length),
     `jv` ("exact" | "fd") and `workspace` (re-use a Krylov workspace across calls -- the
     reference's own TODO at :316); everything else keeps the reference's meaning and default.
     """
+    from .precond import multigrid
+
     callback = callback or (lambda *a: None)
     krylov_kwargs = dict(krylov_kwargs or {})
+    # `N=multigrid` (the function itself): a factory of this solve's own, so its hierarchy goes with the solve
+    own_factories = [multigrid() if P is multigrid else None for P in (N, M)]
+    N, M = (f or P for f, P in zip(own_factories, (N, M)))
     t0 = time.perf_counter_ns()
     if res is None:
         res = u.zero()  # similar(u₀); Enzyme.make_zero!(res)   (:260-261)
@@ -281,9 +297,9 @@ def newton_krylov_(F_: DeviceResidual, u: DeviceArray, p=None, res: DeviceArray 
         # N / M: a preconditioner, or a factory called with this step's operator (e.g. N=jacobi);
         # (; N = N(J), kwargs...), (; M = M(J), kwargs...): the user's krylov_kwargs win (:323-329)
         if N is not None and "N" not in kwargs:
-            kwargs["N"] = N if hasattr(N, "as_c") else N(J)
+            kwargs["N"] = _refreshed(N, J) if hasattr(N, "as_c") else N(J)
         if M is not None and "M" not in kwargs:
-            kwargs["M"] = M if hasattr(M, "as_c") else M(J)
+            kwargs["M"] = _refreshed(M, J) if hasattr(M, "as_c") else M(J)
         krylov_solve_(workspace, J, res, _b_norm=n_res, _u_norm=u_norm, _u_update=u, _f0_is_residual=True, **kwargs)
         n_matvec += workspace.stats.n_matvec
         u_norm = workspace.stats.u_norm
@@ -303,21 +319,40 @@ def newton_krylov_(F_: DeviceResidual, u: DeviceArray, p=None, res: DeviceArray 
     t = (time.perf_counter_ns() - t0) / 1.0e9
     if own_ws:
         workspace.free()
+    for f in own_factories:
+        if f is not None:
+            f.free()
     return u, Result(n_res <= tol, stats, t, n_matvec)
 
 
 def newton_krylov_native(F_: DeviceResidual, u: DeviceArray, p=None, res: DeviceArray | None = None, *,
                          tol_rel: float = 1.0e-6, tol_abs: float = 1.0e-12, max_niter: int = 50,
                          forcing: Forcing | None = EisenstatWalker(), algo: str = "gmres",
-                         krylov_kwargs: dict | None = None, memory: int = 20, jv: str = "exact"):
+                         krylov_kwargs: dict | None = None, memory: int = 20, jv: str = "exact", N=None, M=None):
     """newton_krylov_ with the loop itself in libnkhip.so (nk_newton_krylov, the C/C++ callers' entry
-    point).  Same arguments, same result; returns (u, Result) with the histories of ||F||."""
+    point).  Same arguments, same result; returns (u, Result) with the histories of ||F||.  N / M: a
+    MultigridPreconditioner or the `multigrid` factory only (the C loop refreshes it from each step's u);
+    the other preconditioners are built per step by Python factories, which newton_krylov_ runs."""
+    from .precond import MultigridPreconditioner, _MultigridFactory, multigrid
+
+    if res is None:
+        res = u.zero()
+    pcs = {}
+    for name, P in (("N", N), ("M", M)):
+        if P is None:
+            continue
+        if P is multigrid or isinstance(P, _MultigridFactory):
+            P = P(JacobianOperator(F_, res, u, p, jv=jv))
+        if not isinstance(P, MultigridPreconditioner):
+            raise TypeError(f"newton_krylov_native: {name} must be a MultigridPreconditioner or the multigrid factory "
+                            "(other preconditioners: newton_krylov_)")
+        if name == "M" and str(algo).lstrip(":") == "cg":
+            raise NotImplementedError("algo = :cg with M = multigrid is not supported: use :gmres")
+        pcs[name] = P
     kk = dict(krylov_kwargs or {})
     unknown = set(kk) - {"restart", "reorthogonalization", "itmax", "atol", "rtol"}
     if unknown:
         raise TypeError(f"unsupported Krylov keyword(s): {sorted(unknown)}")
-    if res is None:
-        res = u.zero()
     o = _lib.nk_newton_opts()
     load().nk_newton_defaults(C.byref(o))
     o.tol_rel, o.tol_abs, o.max_niter = float(tol_rel), float(tol_abs), int(max_niter)
@@ -338,6 +373,10 @@ def newton_krylov_native(F_: DeviceResidual, u: DeviceArray, p=None, res: Device
     o.krylov.atol = float(kk.get("atol", o.krylov.atol))
     if "rtol" in kk:
         o.krylov.rtol, o.rtol_user = float(kk["rtol"]), 1
+    if "N" in pcs:
+        o.krylov.N = C.cast(C.pointer(pcs["N"].as_c()), C.c_void_p)
+    if "M" in pcs:
+        o.krylov.M = C.cast(C.pointer(pcs["M"].as_c()), C.c_void_p)
     st = _lib.nk_newton_stats()
     cap = int(max_niter) + 2
     hist = (C.c_double * cap)()

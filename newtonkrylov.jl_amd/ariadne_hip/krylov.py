@@ -208,7 +208,12 @@ def krylov_solve_(ws: KrylovWorkspace, J, b: DeviceArray, *, restart=False, reor
                                       "(ldiv = false), or a factorisation (ilu0)")
         if P is not None and not hasattr(P, "as_c"):
             raise TypeError(f"{name} must be an ariadne_hip preconditioner (DiagonalPreconditioner, "
-                            "UserPreconditioner, GmresPreconditioner, jacobi(J), ilu0(J))")
+                            "UserPreconditioner, GmresPreconditioner, MultigridPreconditioner, jacobi(J), ilu0(J))")
+    from .precond import MultigridPreconditioner
+
+    if ws.algo == "cg" and isinstance(M, MultigridPreconditioner):
+        raise NotImplementedError("algo = :cg with M = multigrid is not supported: use :gmres or :fgmres "
+                                  "(the V-cycle is applied as GMRES's N or M)")
     if ws.algo == "cg" and N is not None:
         raise TypeError("cg! takes its preconditioner as M (Krylov.jl has no right preconditioner for CG)")
     if ws.algo == "cg" and (restart or reorthogonalization):

@@ -1,10 +1,11 @@
 """Preconditioners for the device GMRES / FGMRES / CG: Krylov.jl's right `N` and left `M` (ldiv =
 false: z = P v approximates J^{-1} v; for CG, M is the SPD preconditioner).  SURVEY.md §8f rank 3:
-device Jacobi and ILU(0) preconditioners built from the Jacobian, an inner GMRES, and any other
+device Jacobi and ILU(0) preconditioners built from the Jacobian, an inner GMRES, a geometric multigrid
+V-cycle for the stencil Jacobians (MultigridPreconditioner / `multigrid`), and any other
 preconditioner supplied as device code (UserPreconditioner).
 
 `newton_krylov_(…, N=factory, M=factory)`: a factory is called as `factory(J)` once per Newton step
-(the JacobianOperator of that step) and returns one of these (e.g. `N=jacobi`, `M=ilu0`).
+(the JacobianOperator of that step) and returns one of these (e.g. `N=jacobi`, `M=ilu0`, `N=multigrid`).
 """
 from __future__ import annotations
 
@@ -146,3 +147,166 @@ class Ilu0Preconditioner(Preconditioner):
 def ilu0(J) -> Ilu0Preconditioner:
     """N factory: `N = ilu0` is the device counterpart of `N = (J) -> ilu(collect(J))`."""
     return Ilu0Preconditioner(J)
+
+
+class MultigridPreconditioner(Preconditioner):
+    """One geometric multigrid V-cycle on the stencil Jacobian J(u) = Σ_a k_a δ²_a + diag(s) (NK_PRECOND_MG,
+    DESIGN.md §10): weighted Jacobi smoothing (`nu` pre / post sweeps, `coarse_sweeps` on the coarsest
+    level, weight `omega`, default 2d / (2d + 1)), per axis n -> n // 2 while n > 3 (`max_levels` = 0: until
+    every axis is <= 3), rediscretised coarse operators, linear prolongation, restriction D^-1 P^T.  A fixed
+    linear map: valid as N or M of gmres as well as fgmres.  Built-in stencil residuals, bc_zero_, one
+    rank; everything else raises NotImplementedError.  `update(J)` refreshes s = λ exp(u) for a new u."""
+
+    def __init__(self, J, nu: int = 2, coarse_sweeps: int = 8, omega: float | None = None, max_levels: int = 0):
+        prob = _mg_problem(J)
+        self._create(J.u.ctx, J.u.grid, prob, nu, coarse_sweeps, omega, max_levels)
+        self.update(J)
+
+    def _create(self, ctx, grid, prob, nu, coarse_sweeps, omega, max_levels):
+        import ctypes as C
+
+        self.ctx, self.grid, self.handle = ctx, grid, None
+        self.caller_operator = False  # True: k and s came from from_coefficients, and update(J) is not applied
+        self.opts = _lib.nk_mg_opts(int(nu), int(coarse_sweeps), float(omega or 0.0), int(max_levels))
+        h = C.c_void_p()
+        ctx.check(load().nk_mg_create(ctx.handle, C.byref(prob), C.byref(self.opts), C.byref(h)), "nk_mg_create")
+        self.handle = h
+        self._c = _lib.nk_precond(_lib.NK_PRECOND_MG, None, _lib.NK_USER_PRECOND(), h, None, 0)
+
+    @classmethod
+    def from_coefficients(cls, grid, k, s, *, h=None, ctx=None, nu: int = 2, coarse_sweeps: int = 8,
+                          omega: float | None = None, max_levels: int = 0):
+        """The V-cycle for A = Σ_a k[a] δ²_a(h[a]) + diag(s) on `grid` with caller-supplied coefficients: k per
+        axis, s a DeviceArray on the grid or a constant; h = the spacings (default 1 / (n + 1) per axis).  Such an
+        object keeps the caller's operator: the Newton drivers do not refresh it from the Jacobian (so it also
+        serves a UserResidual); call update(J) yourself to switch it to a built-in J's coefficients."""
+        import ctypes as C
+
+        from .device import default_context
+
+        self = cls.__new__(cls)
+        ctx = ctx or (s.ctx if isinstance(s, DeviceArray) else default_context())
+        if getattr(ctx, "nranks", 1) != 1 or tuple(grid.shape_xyz) != tuple(grid.global_xyz):
+            raise NotImplementedError("multigrid: one rank only (a distributed grid is not implemented)")
+        k = [float(x) for x in (k if hasattr(k, "__len__") else [k] * grid.dim)]
+        if len(k) != grid.dim:
+            raise ValueError("k: one coefficient per axis")
+        h = [float(x) for x in (h if h is not None else [1.0 / (n + 1) for n in grid.shape_xyz])]
+        if len(h) != grid.dim:
+            raise ValueError("h: one spacing per axis")
+        if isinstance(s, DeviceArray) and s.grid != grid:
+            raise ValueError("s must be a DeviceArray on `grid` (or a constant)")
+        prob = grid.geometry_problem()
+        prob.hx, prob.hy, prob.hz = (h + [1.0, 1.0])[:3]
+        self._create(ctx, grid, prob, nu, coarse_sweeps, omega, max_levels)
+        kk = (C.c_double * 3)(*(k + [0.0, 0.0])[:3])
+        sd, sc = (s.ptr, 0.0) if isinstance(s, DeviceArray) else (None, float(s))
+        ctx.check(load().nk_mg_set_operator(self.handle, kk, sd, sc), "nk_mg_set_operator")
+        self.caller_operator = True
+        return self
+
+    def update(self, J) -> "MultigridPreconditioner":
+        """k and s of J(u) at J's current u (nk_mg_set_jacobian): call after u changed."""
+        import ctypes as C
+
+        prob = _mg_problem(J)
+        self.caller_operator = False
+        if J.u.grid != self.grid or J.u.ctx is not self.ctx:
+            raise ValueError("multigrid: J lives on another grid / context than the hierarchy")
+        self.ctx.check(load().nk_mg_set_jacobian(self.handle, C.byref(prob), J.u.ptr), "nk_mg_set_jacobian")
+        return self
+
+    def vcycle(self, v: DeviceArray, z: DeviceArray | None = None) -> DeviceArray:
+        """z = V-cycle(v) (nk_mg_apply, then a sync): the preconditioner by itself, without an operator J."""
+        z = v.zero() if z is None else z
+        self.ctx.check(load().nk_mg_apply(self.handle, z.ptr, v.ptr), "nk_mg_apply")
+        self.ctx.sync()
+        return z
+
+    @property
+    def levels(self) -> list:
+        """Extents (x fastest) of the levels in use, finest first."""
+        import ctypes as C
+
+        n = C.c_int32(0)
+        self.ctx.check(load().nk_mg_levels(self.handle, C.byref(n)), "nk_mg_levels")
+        return multigrid_plan(self.grid.shape_xyz, self.opts.max_levels)[: n.value]
+
+    def as_c(self):
+        return self._c
+
+    def free(self):
+        if getattr(self, "handle", None) and self.ctx.handle:
+            load().nk_mg_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _mg_problem(J):
+    """J's nk_problem if the multigrid preconditioner covers it; NotImplementedError naming the reason if not
+    (checked on the host, before anything touches the device)."""
+    from .problems import UserResidual
+
+    if isinstance(J.f, UserResidual):
+        raise NotImplementedError("multigrid: a user residual has no known stencil coefficients -- build the V-cycle "
+                                  "with MultigridPreconditioner.from_coefficients(grid, k, s)")
+    ctx, grid = J.u.ctx, J.u.grid
+    if getattr(ctx, "nranks", 1) != 1 or tuple(grid.shape_xyz) != tuple(grid.global_xyz):
+        raise NotImplementedError("multigrid: one rank only (a distributed context / slab is not implemented)")
+    prob = J.problem()
+    if prob.bc != _lib.NK_BC_ZERO:
+        raise NotImplementedError("multigrid: bc_zero_ only (periodic boundaries are not implemented)")
+    return prob
+
+
+def multigrid_plan(shape_xyz, max_levels: int = 0) -> list:
+    """The level extents nk_mg_plan gives for a grid (host only, no GPU): [(nx[, ny[, nz]]), ...]."""
+    import ctypes as C
+
+    dim = len(shape_xyz)
+    n = (C.c_int64 * 3)(*(list(shape_xyz) + [1, 1])[:3])
+    ext = (C.c_int64 * (3 * 64))()
+    nl = C.c_int32(0)
+    _lib.check(load().nk_mg_plan(n, int(max_levels), ext, 64, C.byref(nl)), None, "nk_mg_plan")
+    return [tuple(int(ext[3 * l + a]) for a in range(dim)) for l in range(min(nl.value, 64))]
+
+
+class _MultigridFactory:
+    """(J) -> MultigridPreconditioner with one hierarchy kept across calls: allocated for the first J, then
+    only refreshed (s = λ exp(u) and the level diagonals) while the context, grid, spacings and residual kind
+    stay; anything else builds a new hierarchy (and frees the old one)."""
+
+    def __init__(self, opts):
+        self.opts, self.key, self.mg = dict(opts), None, None
+
+    def __call__(self, J):
+        prob = _mg_problem(J)
+        key = (id(J.u.ctx), J.u.grid, prob.kind, prob.hx, prob.hy, prob.hz)
+        if self.mg is None or self.key != key or self.mg.handle is None or self.mg.ctx is not J.u.ctx:
+            self.free()
+            self.key, self.mg = key, MultigridPreconditioner(J, **self.opts)
+            return self.mg
+        return self.mg.update(J)
+
+    def free(self):
+        if self.mg is not None:
+            self.mg.free()
+        self.key, self.mg = None, None
+
+
+def multigrid(J=None, **opts):
+    """N / M factory for newton_krylov_: `N=multigrid` (the defaults) or `N=multigrid(nu=3, ...)`.  The
+    hierarchy is allocated once per Newton solve and reused by every step (as gmres_preconditioner reuses its
+    workspace); each step refreshes s = λ exp(u) and the level diagonals from that step's u.  A factory made by
+    `multigrid(...)` keeps its hierarchy for as long as it lives (`.free()` releases it); `N=multigrid` itself
+    keeps nothing beyond the solve.  Called with an operator, `multigrid(J)` is MultigridPreconditioner(J)."""
+    if J is None:
+        return _MultigridFactory(opts)
+    if opts:
+        raise TypeError("multigrid(J, ...) with options: use MultigridPreconditioner(J, ...) or N=multigrid(...)")
+    return MultigridPreconditioner(J)

@@ -331,6 +331,9 @@ int launch_fd_point(nk_ctx* c, int64_t n, double* w, const double* u, const doub
 int launch_user_epi(nk_ctx* c, int64_t n, int fd, double* out, const double* F0, double eps, int epi,
                     const double* aux, Red* red);
 int launch_user(nk_ctx* c, const StencilIn& in, Red* red);  // nk_user.cpp
+// nk_mg.hip: a multigrid preconditioner follows the Jacobian of each Newton step (nk_mg_set_jacobian), unless its
+// operator came from the caller (nk_mg_set_operator): then it is left as it is
+int mg_refresh(nk_mg* mg, const nk_problem* p, const double* u);
 // roctx range for the lifetime of a scope (shows Newton steps / Krylov solves / GMRES cycles in
 // rocprofv3 --marker-trace timelines; a no-op when no profiler is attached)
 struct Range {

@@ -207,6 +207,7 @@ struct Op {
 //   GMRES  sol, _ = gmres(J, v; itmax); copyto!(z, sol) -- the GmresPreconditioner of
 //          examples/bratu.jl:139-157: Krylov.jl's gmres defaults (memory 20, no restart,
 //          atol = rtol = √eps, x0 = 0) on the same operator, in the preconditioner's own workspace
+//   MG     one multigrid V-cycle (nk_mg.hip): kernels on the context's stream only, no host sync
 int apply_precond(nk_ctx* c, const nk_problem* p, const nk_precond* N, Op& A, int64_t n, double* z, const double* v,
                   bool need_norm, double* znorm) {
     Red rz{};
@@ -236,6 +237,10 @@ int apply_precond(nk_ctx* c, const nk_problem* p, const nk_precond* N, Op& A, in
         nk_krylov_stats is{};
         NK_TRY(gmres(N->inner, p, A, v, &io, &is, nullptr, 0, nullptr));
         NK_TRY(launch_copy(c, n, z, N->inner->x));
+        if (need_norm) NK_TRY(launch_sumsq(c, n, z, &rz));
+    } else if (N->kind == NK_PRECOND_MG) {
+        if (!N->data) return fail(c, NK_E_ARG, "multigrid preconditioner without its hierarchy (nk_mg_create)");
+        NK_TRY(nk_mg_apply(static_cast<nk_mg*>(N->data), z, v));
         if (need_norm) NK_TRY(launch_sumsq(c, n, z, &rz));
     } else {
         return fail(c, NK_E_ARG, "unknown preconditioner kind");
@@ -752,6 +757,8 @@ int nk_krylov_solve(nk_workspace* ws, const nk_problem* p, const double* u, cons
     ws->u_fused = false;
     if (ws->algo == NK_ALGO_CG && o->N && o->N->kind != NK_PRECOND_NONE)
         return fail(c, NK_E_ARG, "the device CG takes no right preconditioner (use GMRES / FGMRES)");
+    if (ws->algo == NK_ALGO_CG && o->M && o->M->kind == NK_PRECOND_MG)
+        return fail(c, NK_E_ARG, "the multigrid V-cycle as CG's M is not supported (use GMRES / FGMRES)");
     int rc = (ws->algo == NK_ALGO_CG) ? cg(ws, A, b, o, st, hist, hist_cap, hist_len)
                                       : gmres(ws, p, A, b, o, st, hist, hist_cap, hist_len);
     if (rc != NK_OK && c->ilu_redo && !ws->u_fused && c->nranks == 1) {

@@ -1,0 +1,597 @@
+// nk_mg.hip -- geometric multigrid preconditioner (NK_PRECOND_MG) for the stencil Jacobians
+//   A_l = Σ_a k_a δ²_a(h_a^l) + diag(s_l)      (Bratu: k = 1, s_0 = λ exp(u); heat: k = θ a Δt, s_0 = -1).
+// One V-cycle from x = 0 per application: weighted Jacobi smoothing, coarse operators rediscretised on the
+// non-nested grids n_{l+1} = n_l / 2, linear prolongation P, restriction R = D^-1 P^T as a gather (no
+// atomics: every application is bit-identical).  The per-point arithmetic lives in device functions on
+// plain pointers, shared by the per-level kernels (global memory) and the coarse tail (k_mg_tail: every
+// level of at most kMgTailPoints points, all of them in one work-group's LDS, one launch).  DESIGN.md §10.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "nk_device.hpp"
+
+namespace nk {
+namespace {
+
+constexpr int kMgMaxLevels = 32;
+constexpr int kMgTailLevels = 12;      // 1024 -> 2 points in 1D is 10 levels
+constexpr int kMgTailPoints = 1024;    // first tail level: at most this many points (5 arrays x < 2 x 1024 x 8 B = 80 KiB LDS)
+constexpr int kMgTailThreads = 1024;
+// LDS of the tail: its levels at least halve, so they hold at most 2 kMgTailPoints - 1 points, five arrays each
+constexpr size_t kMgTailLds = 5 * sizeof(double) * (2 * kMgTailPoints - 1);
+constexpr int kMgMinmaxBlocks = 64;
+
+struct MgLv {
+    int nx, ny, nz, n;
+    double cx, cy, cz;  // k_a / h_a^2 (0 along an unused axis)
+};
+
+// Σ_a c_a (x_- + x_+) at point i, zero Dirichlet boundary
+__device__ __forceinline__ double mg_off(const MgLv& L, const double* x, int i) {
+    const int ix = i % L.nx, t = i / L.nx, iy = t % L.ny, iz = t / L.ny;
+    const double xm = ix > 0 ? x[i - 1] : 0.0, xp = ix + 1 < L.nx ? x[i + 1] : 0.0;
+    double o = L.cx * (xm + xp);
+    if (L.ny > 1) {
+        const double ym = iy > 0 ? x[i - L.nx] : 0.0, yp = iy + 1 < L.ny ? x[i + L.nx] : 0.0;
+        o = o + L.cy * (ym + yp);
+    }
+    if (L.nz > 1) {
+        const int pl = L.nx * L.ny;
+        const double zm = iz > 0 ? x[i - pl] : 0.0, zp = iz + 1 < L.nz ? x[i + pl] : 0.0;
+        o = o + L.cz * (zm + zp);
+    }
+    return o;
+}
+// weighted Jacobi x <- x + ω (b - A x) / diag, written on 1 / diag alone:
+//   x <- (1 - ω) x + ω ((b - Σ_a c_a (x_- + x_+)) / diag);   from x = 0: x = ω (b / diag)
+__device__ __forceinline__ double mg_sweep0_pt(double omega, const double* b, const double* idg, int i) {
+    return omega * (idg[i] * b[i]);
+}
+__device__ __forceinline__ double mg_sweep_pt(const MgLv& L, double omega, double om1, const double* x, const double* b,
+                                              const double* idg, int i) {
+    const double t = b[i] - mg_off(L, x, i);
+    return om1 * x[i] + omega * (idg[i] * t);
+}
+__device__ __forceinline__ double mg_resid_pt(const MgLv& L, const double* x, const double* b, const double* dg, int i) {
+    return b[i] - (mg_off(L, x, i) + dg[i] * x[i]);
+}
+
+// one axis of R = D^-1 P^T for coarse point j (0-based): the fine points lo .. lo + cnt - 1 with integer weights
+// w = (n_f + 1) - |I (n_c + 1) - J (n_f + 1)| (I, J 1-based) and their sum D; an axis that was not coarsened is
+// the identity
+struct MgAx {
+    int lo, cnt, w[4], D;
+};
+__device__ __forceinline__ MgAx mg_rax(int nf, int nc, int j) {
+    MgAx a{j, 1, {1, 0, 0, 0}, 1};
+    if (nf == nc) return a;
+    // the products reach n_f^2 / 2: 64-bit (an axis may have more than 65534 points)
+    const int64_t J = j + 1, F = nf + 1, Cc = nc + 1;
+    int64_t lo = ((J - 1) * F) / Cc + 1, hi = ((J + 1) * F - 1) / Cc;
+    lo = lo < 1 ? 1 : lo;
+    hi = hi > nf ? nf : hi;
+    hi = hi > lo + 3 ? lo + 3 : hi;  // the open interval has length 2 (n_f + 1) / (n_c + 1) <= 4: at most 4 points
+    a.lo = (int)(lo - 1);
+    a.cnt = (int)(hi - lo + 1);
+    a.D = 0;
+    for (int t = 0; t < 4; ++t) {
+        const int64_t d = (lo + t) * Cc - J * F;
+        a.w[t] = t < a.cnt ? (int)(F - (d < 0 ? -d : d)) : 0;
+        a.D += a.w[t];
+    }
+    return a;
+}
+__device__ __forceinline__ double mg_restrict_pt(const MgLv& Lf, const MgLv& Lc, const double* r, int j) {
+    const int jx = j % Lc.nx, t = j / Lc.nx, jy = t % Lc.ny, jz = t / Lc.ny;
+    const MgAx ax = mg_rax(Lf.nx, Lc.nx, jx), ay = mg_rax(Lf.ny, Lc.ny, jy), az = mg_rax(Lf.nz, Lc.nz, jz);
+    double acc = 0.0;
+    for (int c = 0; c < az.cnt; ++c)
+        for (int b = 0; b < ay.cnt; ++b) {
+            const double wyz = (double)az.w[c] * (double)ay.w[b];
+            const int row = ((az.lo + c) * Lf.ny + (ay.lo + b)) * Lf.nx + ax.lo;
+            for (int a = 0; a < ax.cnt; ++a) acc = fma(wyz * (double)ax.w[a], r[row + a], acc);
+        }
+    return acc / ((double)az.D * (double)ay.D * (double)ax.D);
+}
+
+// one axis of P for fine point i (0-based): coarse points j - 1 and j (0-based; outside 0 .. n_c - 1: the
+// boundary, 0) with weights 1 - w and w, w = (q mod (n_f + 1)) / (n_f + 1), q = (i + 1) (n_c + 1), j = q / (n_f + 1)
+struct MgPx {
+    int j;
+    double w;
+};
+__device__ __forceinline__ MgPx mg_pax(int nf, int nc, int i) {
+    if (nf == nc) return MgPx{i + 1, 0.0};
+    const int64_t q = (int64_t)(i + 1) * (nc + 1), F = nf + 1;  // 64-bit: q reaches n_f^2 / 2
+    return MgPx{(int)(q / F), (double)(q % F) / (double)F};
+}
+__device__ __forceinline__ double mg_prolong_pt(const MgLv& Lf, const MgLv& Lc, const double* e, int i) {
+    const int ix = i % Lf.nx, t = i / Lf.nx, iy = t % Lf.ny, iz = t / Lf.ny;
+    const MgPx px = mg_pax(Lf.nx, Lc.nx, ix), py = mg_pax(Lf.ny, Lc.ny, iy), pz = mg_pax(Lf.nz, Lc.nz, iz);
+    double vz[2];
+    for (int c = 0; c < 2; ++c) {
+        const int jz = pz.j - 1 + c;
+        double vy[2];
+        for (int b = 0; b < 2; ++b) {
+            const int jy = py.j - 1 + b;
+            double lo = 0.0, hi = 0.0;
+            if (jz >= 0 && jz < Lc.nz && jy >= 0 && jy < Lc.ny) {
+                const int row = (jz * Lc.ny + jy) * Lc.nx;
+                if (px.j - 1 >= 0) lo = e[row + px.j - 1];
+                if (px.j < Lc.nx) hi = e[row + px.j];
+            }
+            vy[b] = (1.0 - px.w) * lo + px.w * hi;
+        }
+        vz[c] = (1.0 - py.w) * vy[0] + py.w * vy[1];
+    }
+    return (1.0 - pz.w) * vz[0] + pz.w * vz[1];
+}
+
+// ------------------------------------------------------------------------------ per-level kernels
+__global__ __launch_bounds__(kBlock) void k_mg_sweep0(int n, double omega, double* x, const double* b,
+                                                     const double* __restrict__ idg) {
+    NK_CHUNKED(i, n) x[i] = mg_sweep0_pt(omega, b, idg, (int)i);
+}
+// xn must not alias x (the ping-pong pair); b is only read at the point written
+__global__ __launch_bounds__(kBlock) void k_mg_sweep(MgLv L, double omega, double om1, double* xn, const double* __restrict__ x,
+                                                    const double* b, const double* __restrict__ idg) {
+    NK_CHUNKED(i, L.n) xn[i] = mg_sweep_pt(L, omega, om1, x, b, idg, (int)i);
+}
+__global__ __launch_bounds__(kBlock) void k_mg_resid(MgLv L, double* __restrict__ r, const double* __restrict__ x,
+                                                    const double* __restrict__ b, const double* __restrict__ dg) {
+    NK_CHUNKED(i, L.n) r[i] = mg_resid_pt(L, x, b, dg, (int)i);
+}
+__global__ __launch_bounds__(kBlock) void k_mg_restrict(MgLv Lf, MgLv Lc, double* __restrict__ bc, const double* __restrict__ r) {
+    NK_CHUNKED(j, Lc.n) bc[j] = mg_restrict_pt(Lf, Lc, r, (int)j);
+}
+__global__ __launch_bounds__(kBlock) void k_mg_prolong(MgLv Lf, MgLv Lc, double* __restrict__ x, const double* __restrict__ e) {
+    NK_CHUNKED(i, Lf.n) x[i] = x[i] + mg_prolong_pt(Lf, Lc, e, (int)i);
+}
+// set-up: diag = dsum + s (dsum = Σ_a -2 c_a, summed in axis order on the host) and 1 / diag
+__global__ __launch_bounds__(kBlock) void k_mg_diag(int n, double dsum, const double* __restrict__ s, double* __restrict__ dg,
+                                                   double* __restrict__ idg) {
+    NK_CHUNKED(i, n) {
+        const double d = dsum + s[i];
+        dg[i] = d;
+        idg[i] = 1.0 / d;
+    }
+}
+// set-up: per-block minimum and maximum of the diagonal (NaN counts as a failure: part = {NaN-safe -inf, +inf})
+__global__ __launch_bounds__(kBlock) void k_mg_minmax(int n, const double* __restrict__ dg, double* __restrict__ part) {
+    __shared__ double smin[kBlock], smax[kBlock];
+    double lo = INFINITY, hi = -INFINITY;
+    bool bad = false;
+    NK_CHUNKED(i, n) {
+        const double d = dg[i];
+        bad = bad || !(d == d);
+        lo = fmin(lo, d);
+        hi = fmax(hi, d);
+    }
+    if (bad) { lo = -INFINITY; hi = INFINITY; }
+    smin[threadIdx.x] = lo;
+    smax[threadIdx.x] = hi;
+    __syncthreads();
+    for (int s = kBlock / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            smin[threadIdx.x] = fmin(smin[threadIdx.x], smin[threadIdx.x + s]);
+            smax[threadIdx.x] = fmax(smax[threadIdx.x], smax[threadIdx.x + s]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x] = smin[0];
+        part[2 * blockIdx.x + 1] = smax[0];
+    }
+}
+
+// ------------------------------------------------------------------------------ the coarse tail
+// Levels t .. L - 1 (the first with at most kMgTailPoints points) in one work-group: each level's five arrays
+// (the ping-pong pair xa / xb, b, 1 / diag, diag) live in LDS, a barrier between sweeps.  The x of a level after
+// k sweeps is in xa for odd k, xb for even k (the first sweep, from zero, writes xa).
+struct MgTail {
+    int nlev, nu, cs;
+    double omega, om1;
+    MgLv lv[kMgTailLevels];
+    int off[kMgTailLevels];  // first double of the level's arrays in LDS
+    const double* dg[kMgTailLevels];
+    const double* idg[kMgTailLevels];
+    const double* b;  // right-hand side of the tail's first level
+    double* x;        // its result
+};
+
+__device__ __forceinline__ void mg_tail_sweeps(const MgLv& L, double omega, double om1, double* xa, double* xb, const double* b,
+                                               const double* idg, int done, int sweeps) {
+    for (int s = 0; s < sweeps; ++s, ++done) {
+        if (done == 0) {
+            for (int i = threadIdx.x; i < L.n; i += kMgTailThreads) xa[i] = mg_sweep0_pt(omega, b, idg, i);
+        } else {
+            const double* x = (done & 1) ? xa : xb;
+            double* xn = (done & 1) ? xb : xa;
+            for (int i = threadIdx.x; i < L.n; i += kMgTailThreads) xn[i] = mg_sweep_pt(L, omega, om1, x, b, idg, i);
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(kMgTailThreads) void k_mg_tail(MgTail T) {
+    extern __shared__ double mg_lds[];
+#define MG_XA(l) (mg_lds + T.off[l])
+#define MG_XB(l) (mg_lds + T.off[l] + T.lv[l].n)
+#define MG_B(l) (mg_lds + T.off[l] + 2 * T.lv[l].n)
+#define MG_IDG(l) (mg_lds + T.off[l] + 3 * T.lv[l].n)
+#define MG_DG(l) (mg_lds + T.off[l] + 4 * T.lv[l].n)
+    for (int l = 0; l < T.nlev; ++l)
+        for (int i = threadIdx.x; i < T.lv[l].n; i += kMgTailThreads) {
+            MG_IDG(l)[i] = T.idg[l][i];
+            MG_DG(l)[i] = T.dg[l][i];
+            if (l == 0) MG_B(0)[i] = T.b[i];
+        }
+    __syncthreads();
+    // descent
+    for (int l = 0; l < T.nlev; ++l) {
+        const MgLv& L = T.lv[l];
+        const bool last = l == T.nlev - 1;
+        mg_tail_sweeps(L, T.omega, T.om1, MG_XA(l), MG_XB(l), MG_B(l), MG_IDG(l), 0, last ? T.cs : T.nu);
+        if (last) break;
+        const double* x = (T.nu & 1) ? MG_XA(l) : MG_XB(l);
+        double* r = (T.nu & 1) ? MG_XB(l) : MG_XA(l);
+        for (int i = threadIdx.x; i < L.n; i += kMgTailThreads) r[i] = mg_resid_pt(L, x, MG_B(l), MG_DG(l), i);
+        __syncthreads();
+        const MgLv& Lc = T.lv[l + 1];
+        for (int j = threadIdx.x; j < Lc.n; j += kMgTailThreads) MG_B(l + 1)[j] = mg_restrict_pt(L, Lc, r, j);
+        __syncthreads();
+    }
+    // ascent
+    for (int l = T.nlev - 2; l >= 0; --l) {
+        const MgLv& L = T.lv[l];
+        const MgLv& Lc = T.lv[l + 1];
+        const int kc = (l + 1 == T.nlev - 1) ? T.cs : 2 * T.nu;  // sweeps level l + 1 has seen
+        const double* e = (kc & 1) ? MG_XA(l + 1) : MG_XB(l + 1);
+        double* x = (T.nu & 1) ? MG_XA(l) : MG_XB(l);
+        for (int i = threadIdx.x; i < L.n; i += kMgTailThreads) x[i] = x[i] + mg_prolong_pt(L, Lc, e, i);
+        __syncthreads();
+        mg_tail_sweeps(L, T.omega, T.om1, MG_XA(l), MG_XB(l), MG_B(l), MG_IDG(l), T.nu, T.nu);
+    }
+    const int k0 = T.nlev == 1 ? T.cs : 2 * T.nu;
+    const double* x0 = (k0 & 1) ? MG_XA(0) : MG_XB(0);
+    for (int i = threadIdx.x; i < T.lv[0].n; i += kMgTailThreads) T.x[i] = x0[i];
+#undef MG_XA
+#undef MG_XB
+#undef MG_B
+#undef MG_IDG
+#undef MG_DG
+}
+
+// host: the level extents (all integer arithmetic)
+int mg_plan(const int64_t n0[3], int max_levels, int64_t (*ext)[3]) {
+    int64_t n[3] = {n0[0], n0[1], n0[2]};
+    int L = 0;
+    for (;;) {
+        for (int a = 0; a < 3; ++a) ext[L][a] = n[a];
+        ++L;
+        if (L == kMgMaxLevels || (max_levels > 0 && L >= max_levels)) break;
+        if (n[0] <= 3 && n[1] <= 3 && n[2] <= 3) break;
+        for (int a = 0; a < 3; ++a)
+            if (n[a] > 3) n[a] /= 2;
+    }
+    return L;
+}
+
+}  // namespace
+}  // namespace nk
+
+using namespace nk;
+
+struct nk_mg {
+    nk_ctx* c = nullptr;
+    nk_problem prob{};       // the geometry it was created for
+    int dim = 1;
+    int nlev_alloc = 0;      // levels of the plan
+    int nlev = 0;            // levels in use (set-up may truncate)
+    int tail = 0;            // first level of the one-launch coarse tail (== nlev_alloc: none)
+    int nu = 2, cs = 8;
+    double omega = 0.0;
+    bool ready = false;      // an operator has been set
+    bool user_op = false;    // ... by nk_mg_set_operator: the caller's, not refreshed from a Jacobian by the Newton loop
+    MgLv lv[kMgMaxLevels];
+    double len[3] = {0, 0, 0};  // L_a = (n_a^0 + 1) h_a^0
+    double h0[3] = {0, 0, 0};
+    // per level (device): ping-pong pair, right-hand side (level 0: the caller's v), s, diag, 1 / diag
+    double *xa[kMgMaxLevels] = {}, *xb[kMgMaxLevels] = {}, *b[kMgMaxLevels] = {}, *s[kMgMaxLevels] = {},
+           *dg[kMgMaxLevels] = {}, *idg[kMgMaxLevels] = {};
+    double* part = nullptr;  // set-up: kMgMinmaxBlocks (min, max) pairs per level
+    size_t tail_lds = 0;
+};
+
+namespace {
+
+int mg_launch_sweep0(nk_mg* m, int l, double* x, const double* b) {
+    const MgLv& L = m->lv[l];
+    return launch(m->c, "mg_sweep0", 24.0 * L.n, [&] {
+        hipLaunchKernelGGL(k_mg_sweep0, dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L.n, m->omega, x, b, m->idg[l]);
+    });
+}
+int mg_launch_sweep(nk_mg* m, int l, double* xn, const double* x, const double* b) {
+    const MgLv& L = m->lv[l];
+    return launch(m->c, "mg_sweep", 32.0 * L.n, [&] {
+        hipLaunchKernelGGL(k_mg_sweep, dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, m->omega, 1.0 - m->omega, xn, x, b,
+                           m->idg[l]);
+    });
+}
+// `sweeps` sweeps on level l after `done` earlier ones; the x so far is *cur (unused when done == 0), the sweeps
+// ping-pong between xa / xb and the last one writes `final` when given.  *cur = where x is afterwards.
+int mg_sweeps(nk_mg* m, int l, const double* b, int done, int sweeps, double** cur, double* final) {
+    for (int s = 0; s < sweeps; ++s, ++done) {
+        double* dst = (final && s == sweeps - 1) ? final : (*cur == m->xa[l] ? m->xb[l] : m->xa[l]);
+        if (done == 0) NK_TRY(mg_launch_sweep0(m, l, dst, b));
+        else NK_TRY(mg_launch_sweep(m, l, dst, *cur, b));
+        *cur = dst;
+    }
+    return NK_OK;
+}
+
+int mg_restrict(nk_mg* m, int l, double* bc, const double* r, const char* name) {
+    const MgLv &Lf = m->lv[l], &Lc = m->lv[l + 1];
+    return launch(m->c, name, 8.0 * Lf.n + 8.0 * Lc.n, [&] {
+        hipLaunchKernelGGL(k_mg_restrict, dim3(wide_blocks(Lc.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, bc, r);
+    });
+}
+
+int mg_free(nk_mg* m) {
+    for (int l = 0; l < kMgMaxLevels; ++l)
+        for (double* q : {m->xa[l], m->xb[l], m->b[l], m->s[l], m->dg[l], m->idg[l]})
+            if (q) (void)hipFree(q);
+    if (m->part) (void)hipFree(m->part);
+    delete m;
+    return NK_OK;
+}
+
+bool mg_kind_ok(int kind) { return kind >= NK_BRATU1D && kind <= NK_HEAT3D_TRAPEZOID; }
+
+// diag and 1 / diag of every level from k and s_0 (already in m->s[0]); level 0's from nk_jacobian_diag when
+// `jac` (bit-identical to J's own diagonal); then the sign check that may truncate the hierarchy
+int mg_setup(nk_mg* m, const double k[3], const nk_problem* jac, const double* u) {
+    nk_ctx* c = m->c;
+    for (int l = 0; l < m->nlev_alloc; ++l) {
+        MgLv& L = m->lv[l];
+        const int ext[3] = {L.nx, L.ny, L.nz};
+        double cc[3] = {0.0, 0.0, 0.0}, dsum = 0.0;
+        for (int a = 0; a < m->dim; ++a) {
+            const double h = l == 0 ? m->h0[a] : m->len[a] / (double)(ext[a] + 1);
+            cc[a] = k[a] / (h * h);
+            dsum = a == 0 ? -2.0 * cc[a] : dsum + -2.0 * cc[a];
+        }
+        L.cx = cc[0]; L.cy = cc[1]; L.cz = cc[2];
+        if (l > 0) NK_TRY(mg_restrict(m, l - 1, m->s[l], m->s[l - 1], "mg_setup_restrict"));
+        if (l == 0 && jac) {
+            NK_TRY(launch_jdiag(c, jac, m->dg[0], u, 0));
+            NK_TRY(launch_jdiag(c, jac, m->idg[0], u, 1));
+        } else {
+            NK_TRY(launch(c, "mg_setup_diag", 24.0 * L.n, [&] {
+                hipLaunchKernelGGL(k_mg_diag, dim3(wide_blocks(L.n)), dim3(kBlock), 0, c->stream, L.n, dsum, m->s[l], m->dg[l],
+                                   m->idg[l]);
+            }));
+        }
+        const int g = std::min(kMgMinmaxBlocks, wide_blocks(L.n));
+        NK_TRY(launch(c, "mg_setup_minmax", 8.0 * L.n, [&] {
+            hipLaunchKernelGGL(k_mg_minmax, dim3(g), dim3(kBlock), 0, c->stream, L.n, m->dg[l], m->part + 2 * kMgMinmaxBlocks * l);
+        }));
+    }
+    std::vector<double> part((size_t)2 * kMgMinmaxBlocks * m->nlev_alloc);
+    NK_HIP(c, hipMemcpyAsync(part.data(), m->part, part.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    NK_HIP(c, hipStreamSynchronize(c->stream));
+    int ok = 0;
+    for (; ok < m->nlev_alloc; ++ok) {
+        const int g = std::min(kMgMinmaxBlocks, wide_blocks(m->lv[ok].n));
+        double lo = INFINITY, hi = -INFINITY;
+        for (int b = 0; b < g; ++b) {
+            lo = std::fmin(lo, part[(size_t)2 * (kMgMinmaxBlocks * ok + b)]);
+            hi = std::fmax(hi, part[(size_t)2 * (kMgMinmaxBlocks * ok + b) + 1]);
+        }
+        if (!(lo > 0.0 || hi < 0.0) || std::isinf(lo) || std::isinf(hi)) break;
+    }
+    m->ready = false;
+    if (ok == 0) return fail(c, NK_E_ARG, "multigrid: the diagonal of the operator changes sign, vanishes or is not finite");
+    m->nlev = ok;
+    m->ready = true;
+    return NK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nk_mg_plan(const int64_t n[3], int32_t max_levels, int64_t* extents, int32_t cap, int32_t* nlevels) {
+    if (!n || !nlevels || n[0] < 1 || n[1] < 1 || n[2] < 1 || max_levels < 0 || cap < 0 || (cap > 0 && !extents)) return NK_E_ARG;
+    int64_t ext[kMgMaxLevels][3];
+    const int L = mg_plan(n, max_levels, ext);
+    for (int l = 0; l < L && l < cap; ++l)
+        for (int a = 0; a < 3; ++a) extents[3 * l + a] = ext[l][a];
+    *nlevels = L;
+    return NK_OK;
+}
+
+int nk_mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, nk_mg** out) {
+    if (!c || !p || !out) return NK_E_ARG;
+    if (nk_is_user(p->kind) || !mg_kind_ok(p->kind))
+        return fail(c, NK_E_ARG, "multigrid: built-in stencil kinds only (a user residual's coefficients are unknown; "
+                                 "give them with nk_mg_set_operator on a built-in kind's grid)");
+    if (p->bc != NK_BC_ZERO) return fail(c, NK_E_ARG, "multigrid: bc_zero! only (periodic boundaries are not implemented)");
+    if (c->nranks != 1) return fail(c, NK_E_ARG, "multigrid: one rank only (a distributed context is not implemented)");
+    Geo g;
+    NK_TRY(geometry(c, p, &g));
+    if (g.n >= ((int64_t)1 << 31)) return fail(c, NK_E_ARG, "multigrid: at most 2^31 - 1 points");
+    const int nu = opts && opts->nu ? opts->nu : 2, cs = opts && opts->coarse_sweeps ? opts->coarse_sweeps : 8;
+    const double omega = opts && opts->omega != 0.0 ? opts->omega : 2.0 * g.dim / (2.0 * g.dim + 1.0);
+    if (nu < 1 || cs < 1 || !(omega > 0.0) || (opts && opts->max_levels < 0))
+        return fail(c, NK_E_ARG, "multigrid: nu >= 1, coarse_sweeps >= 1, omega > 0, max_levels >= 0");
+    nk_mg* m = new nk_mg();
+    m->c = c;
+    m->prob = *p;
+    m->dim = g.dim;
+    m->nu = nu;
+    m->cs = cs;
+    m->omega = omega;
+    const int64_t n0[3] = {p->nx, p->ny, p->nz};
+    const double h[3] = {p->hx, p->hy, p->hz};
+    int64_t ext[kMgMaxLevels][3];
+    m->nlev_alloc = mg_plan(n0, opts ? opts->max_levels : 0, ext);
+    for (int a = 0; a < 3; ++a) {
+        m->h0[a] = h[a];
+        m->len[a] = (double)(n0[a] + 1) * h[a];
+    }
+    m->tail = m->nlev_alloc;
+    for (int l = 0; l < m->nlev_alloc; ++l) {
+        MgLv& L = m->lv[l];
+        L.nx = (int)ext[l][0]; L.ny = (int)ext[l][1]; L.nz = (int)ext[l][2];
+        L.n = L.nx * L.ny * L.nz;
+        L.cx = L.cy = L.cz = 0.0;
+        if (m->tail == m->nlev_alloc && L.n <= kMgTailPoints && m->nlev_alloc - l <= kMgTailLevels) m->tail = l;
+        const size_t bytes = sizeof(double) * (size_t)L.n;
+        bool ok = true;
+        for (double** q : {&m->xa[l], &m->xb[l], &m->s[l], &m->dg[l], &m->idg[l]}) ok = ok && hipMalloc(q, bytes) == hipSuccess;
+        if (l > 0) ok = ok && hipMalloc(&m->b[l], bytes) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            mg_free(m);
+            return fail(c, NK_E_NOMEM, "multigrid: out of device memory for the hierarchy");
+        }
+    }
+    if (hipMalloc(&m->part, sizeof(double) * 2 * kMgMinmaxBlocks * (size_t)m->nlev_alloc) != hipSuccess) {
+        mg_free(m);
+        return fail(c, NK_E_NOMEM, "multigrid: out of device memory");
+    }
+    if (m->tail < m->nlev_alloc) {
+        size_t pts = 0;
+        for (int l = m->tail; l < m->nlev_alloc; ++l) pts += (size_t)m->lv[l].n;
+        m->tail_lds = 5 * sizeof(double) * pts;
+        // the same limit for every hierarchy (a per-hierarchy value could lower it under an earlier, larger tail)
+        hipError_t e = m->tail_lds <= kMgTailLds
+                           ? hipFuncSetAttribute(reinterpret_cast<const void*>(k_mg_tail), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)kMgTailLds)
+                           : hipErrorInvalidValue;
+        if (e != hipSuccess) {
+            mg_free(m);
+            return fail(c, NK_E_HIP, std::string("multigrid: LDS for the coarse tail: ") + hipGetErrorString(e));
+        }
+    }
+    m->nlev = m->nlev_alloc;
+    *out = m;
+    return NK_OK;
+}
+
+int nk_mg_destroy(nk_mg* m) {
+    if (!m) return NK_OK;
+    (void)hipStreamSynchronize(m->c->stream);
+    return mg_free(m);
+}
+
+int nk_mg_levels(nk_mg* m, int32_t* nlevels) {
+    if (!m || !nlevels) return NK_E_ARG;
+    *nlevels = m->nlev;
+    return NK_OK;
+}
+
+int nk_mg_set_operator(nk_mg* m, const double k[3], const double* s_dev, double s_const) {
+    if (!m || !k) return NK_E_ARG;
+    nk_ctx* c = m->c;
+    if (s_dev) NK_TRY(launch_copy(c, m->lv[0].n, m->s[0], s_dev));
+    else NK_TRY(launch_fill(c, m->lv[0].n, m->s[0], s_const));
+    m->user_op = true;
+    return mg_setup(m, k, nullptr, nullptr);
+}
+
+int nk_mg_set_jacobian(nk_mg* m, const nk_problem* p, const double* u) {
+    if (!m || !p || !u) return NK_E_ARG;
+    nk_ctx* c = m->c;
+    if (p->kind != m->prob.kind || p->nx != m->prob.nx || p->ny != m->prob.ny || p->nz != m->prob.nz || p->hx != m->prob.hx ||
+        (m->dim >= 2 && p->hy != m->prob.hy) || (m->dim == 3 && p->hz != m->prob.hz) || p->bc != NK_BC_ZERO)
+        return fail(c, NK_E_ARG, "multigrid: the problem does not match the hierarchy's (kind, grid, spacings, bc_zero!)");
+    double k[3] = {0.0, 0.0, 0.0};
+    const int64_t n = m->lv[0].n;
+    if (nk_is_heat(p->kind)) {
+        const int sch = nk_scheme(p->kind);
+        const double theta = sch == 1 ? 1.0 - p->alpha : (sch == 2 ? 0.5 : 1.0);
+        for (int a = 0; a < m->dim; ++a) k[a] = theta * p->a * p->dt;
+        NK_TRY(launch_fill(c, n, m->s[0], -1.0));
+    } else {
+        for (int a = 0; a < m->dim; ++a) k[a] = 1.0;
+        NK_TRY(launch_exp(c, n, m->s[0], u));  // the stencils' own correctly rounded exp
+        NK_TRY(launch_scal(c, n, p->lambda, m->s[0]));
+    }
+    m->user_op = false;
+    return mg_setup(m, k, p, u);
+}
+
+}  // extern "C"
+
+// the Newton loop's refresh before each solve: J(u)'s coefficients, unless the caller set the operator itself
+int nk::mg_refresh(nk_mg* m, const nk_problem* p, const double* u) {
+    if (!m) return NK_E_ARG;
+    if (m->user_op) return m->ready ? NK_OK : fail(m->c, NK_E_STATE, "multigrid: no operator set");
+    return nk_mg_set_jacobian(m, p, u);
+}
+
+extern "C" {
+
+int nk_mg_apply(nk_mg* m, double* z, const double* v) {
+    if (!m || !z || !v) return NK_E_ARG;
+    nk_ctx* c = m->c;
+    if (!m->ready) return fail(c, NK_E_STATE, "multigrid: no operator set (nk_mg_set_jacobian / nk_mg_set_operator)");
+    const int L = m->nlev;
+    const int G = std::min(m->tail, L);  // levels 0 .. G - 1 run per-level kernels, G .. L - 1 the tail launch
+    double* cur[kMgMaxLevels] = {};
+    // descent
+    for (int l = 0; l < G; ++l) {
+        const double* b = l == 0 ? v : m->b[l];
+        if (l == L - 1) {  // the coarsest level, too large for the tail
+            NK_TRY(mg_sweeps(m, l, b, 0, m->cs, &cur[l], l == 0 ? z : nullptr));
+            break;
+        }
+        NK_TRY(mg_sweeps(m, l, b, 0, m->nu, &cur[l], nullptr));
+        double* r = cur[l] == m->xa[l] ? m->xb[l] : m->xa[l];
+        const MgLv& Lv = m->lv[l];
+        NK_TRY(launch(c, "mg_resid", 32.0 * Lv.n, [&] {
+            hipLaunchKernelGGL(k_mg_resid, dim3(wide_blocks(Lv.n)), dim3(kBlock), 0, c->stream, Lv, r, cur[l], b, m->dg[l]);
+        }));
+        NK_TRY(mg_restrict(m, l, m->b[l + 1], r, "mg_restrict"));
+    }
+    if (G < L) {
+        MgTail T{};
+        T.nlev = L - G;
+        T.nu = m->nu;
+        T.cs = m->cs;
+        T.omega = m->omega;
+        T.om1 = 1.0 - m->omega;
+        double pts = 0.0;
+        size_t lds = 0;
+        for (int l = G; l < L; ++l) {
+            T.lv[l - G] = m->lv[l];
+            T.off[l - G] = (int)(lds / sizeof(double));
+            T.dg[l - G] = m->dg[l];
+            T.idg[l - G] = m->idg[l];
+            pts += m->lv[l].n;
+            lds += 5 * sizeof(double) * (size_t)m->lv[l].n;
+        }
+        T.b = G == 0 ? v : m->b[G];
+        T.x = G == 0 ? z : m->xa[G];
+        cur[G] = T.x;
+        NK_TRY(launch(c, "mg_tail", 16.0 * pts + 16.0 * m->lv[G].n, [&] {
+            hipLaunchKernelGGL(k_mg_tail, dim3(1), dim3(kMgTailThreads), lds, c->stream, T);
+        }));
+    }
+    // ascent
+    for (int l = std::min(G, L - 1) - 1; l >= 0; --l) {
+        const MgLv &Lf = m->lv[l], &Lc = m->lv[l + 1];
+        NK_TRY(launch(c, "mg_prolong", 16.0 * Lf.n + 8.0 * Lc.n, [&] {
+            hipLaunchKernelGGL(k_mg_prolong, dim3(wide_blocks(Lf.n)), dim3(kBlock), 0, c->stream, Lf, Lc, cur[l], cur[l + 1]);
+        }));
+        NK_TRY(mg_sweeps(m, l, l == 0 ? v : m->b[l], m->nu, m->nu, &cur[l], l == 0 ? z : nullptr));
+    }
+    return NK_OK;
+}
+
+}  // extern "C"

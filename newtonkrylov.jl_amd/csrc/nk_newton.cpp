@@ -76,6 +76,15 @@ int nk_newton_krylov(nk_ctx* c, const nk_problem* p, double* u, double* res, con
         ko.u_norm = u_norm;
         ko.u_update = u;    // u .-= d fused into the solve's last pass (d = workspace.x is not stored)
         ko.f0_is_residual = 1;  // res = F(u) was just computed by nk_residual_norm
+        // a multigrid preconditioner follows the Jacobian: refresh its s = λ exp(u) (and the level diagonals);
+        // one whose operator the caller set (nk_mg_set_operator) is left alone
+        for (const nk_precond* P : {ko.N, ko.M})
+            if (P && P->kind == NK_PRECOND_MG) {
+                if (!P->data) rc = nk::fail(c, NK_E_ARG, "multigrid preconditioner without its hierarchy (nk_mg_create)");
+                else rc = nk::mg_refresh(static_cast<nk_mg*>(P->data), p, u);
+                if (rc != NK_OK) break;
+            }
+        if (rc != NK_OK) break;
         nk_krylov_stats ks{};
         const double* F0 = ko.jv_mode == NK_JV_FD ? res : nullptr;
         if ((rc = nk_krylov_solve(ws, p, u, F0, res, &ko, &ks, nullptr, 0, nullptr)) != NK_OK) break;

@@ -2,7 +2,8 @@
 // 2D Bratu on an N x N grid, u0 = sin(pi x) sin(pi y), newton_krylov! with GMRES(memory) and the
 // Eisenstat-Walker forcing (src/Ariadne.jl:288-372), FD or exact Jv.  Prints one JSON line.
 //
-//   bin/bratu2d_newton [N=256] [jv=fd|exact] [memory=30] [restart=1]
+//   bin/bratu2d_newton [N=256] [jv=fd|exact] [memory=30] [restart=1] [--mg]
+// --mg (anywhere on the line): the geometric multigrid V-cycle as the right preconditioner N (NK_PRECOND_MG).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -22,6 +23,13 @@
     } while (0)
 
 int main(int argc, char** argv) {
+    bool use_mg = false;
+    int nargs = 1;
+    for (int i = 1; i < argc; ++i) {  // strip --mg, keep the positional arguments
+        if (std::strcmp(argv[i], "--mg") == 0) use_mg = true;
+        else argv[nargs++] = argv[i];
+    }
+    argc = nargs;
     const int64_t N = argc > 1 ? std::atoll(argv[1]) : 256;
     const bool fd = argc > 2 ? std::strcmp(argv[2], "exact") != 0 : true;
     const int memory = argc > 3 ? std::atoi(argv[3]) : 30;
@@ -55,6 +63,14 @@ int main(int argc, char** argv) {
     o.memory = memory;
     o.krylov.restart = restart;
     o.krylov.jv_mode = fd ? NK_JV_FD : NK_JV_EXACT;
+    nk_mg* mg = nullptr;
+    nk_precond Nmg{};
+    if (use_mg) {
+        CHECK(ctx, nk_mg_create(ctx, &p, nullptr, &mg));  // the Newton loop refreshes it from each step's u
+        Nmg.kind = NK_PRECOND_MG;
+        Nmg.data = mg;
+        o.krylov.N = &Nmg;
+    }
     nk_newton_stats st;
     double hist[64];
     int64_t nh = 0;
@@ -65,12 +81,13 @@ int main(int argc, char** argv) {
     CHECK(ctx, nk_memcpy_d2h(ctx, host.data(), u, N * N));
     double umax = 0.0;
     for (double v : host) umax = std::fmax(umax, std::fabs(v));
-    std::printf("{\"N\": %lld, \"jv\": \"%s\", \"solved\": %s, \"outer\": %lld, \"inner\": %lld, \"n_matvec\": %lld, "
+    std::printf("{\"N\": %lld, \"jv\": \"%s\", %s\"solved\": %s, \"outer\": %lld, \"inner\": %lld, \"n_matvec\": %lld, "
                 "\"n_res\": %.17g, \"tol\": %.17g, \"u_max\": %.17g, \"seconds\": %.6f, \"n_res_history\": [",
-                (long long)N, fd ? "fd" : "exact", st.solved ? "true" : "false", (long long)st.outer_iterations,
+                (long long)N, fd ? "fd" : "exact", use_mg ? "\"mg\": true, " : "", st.solved ? "true" : "false", (long long)st.outer_iterations,
                 (long long)st.inner_iterations, (long long)st.n_matvec, st.n_res, st.tol, umax, secs);
     for (int64_t k = 0; k < nh && k < 64; ++k) std::printf("%s%.17g", k ? ", " : "", hist[k]);
     std::printf("]}\n");
+    if (mg) CHECK(ctx, nk_mg_destroy(mg));
     CHECK(ctx, nk_vec_free(ctx, u));
     CHECK(ctx, nk_vec_free(ctx, res));
     nk_ctx_destroy(ctx);

@@ -440,6 +440,73 @@ HipGmresPreconditioner(J::Ariadne.JacobianOperator, itmax::Integer) =
     HipGmresPreconditioner(Krylov.krylov_workspace(:gmres, KrylovConstructor(J.res); memory = 20), itmax)
 nkprecond(P::HipGmresPreconditioner) = NkPrecond(NK_PRECOND_GMRES, C_NULL, C_NULL, C_NULL, P.ws.ptr, P.itmax)
 
+# Geometric multigrid V-cycle for the stencil Jacobians (NK_PRECOND_MG, nkhip.h): built-in residuals,
+# bc_zero!, one rank.  `N = hip_multigrid` is a factory: one hierarchy per (context, grid, kind), refreshed
+# from each Newton step's u (nk_mg_set_jacobian).  Valid for :gmres and :fgmres, as N or M.
+const NK_PRECOND_MG = Int32(5)
+struct NkMgOpts
+    nu::Int32
+    coarse_sweeps::Int32
+    omega::Float64
+    max_levels::Int32
+end
+mutable struct HipMultigridPreconditioner <: HipPreconditioner
+    ptr::Ptr{Cvoid}
+    ctx::Any
+    function HipMultigridPreconditioner(J::Ariadne.JacobianOperator; nu = 2, coarse_sweeps = 8, omega = 0.0, max_levels = 0)
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        opts = NkMgOpts(nu, coarse_sweeps, omega, max_levels)
+        check(ccall((:nk_mg_create, libnkhip), Cint, (VP, Ref{NkProblem}, Ref{NkMgOpts}, Ref{Ptr{Cvoid}}),
+                    J.u.ctx.ptr, problem(J.f, J.u, J.p), opts, out), J.u.ctx, "nk_mg_create")
+        P = new(out[], J.u.ctx)
+        finalizer(P) do q
+            q.ptr == C_NULL || ccall((:nk_mg_destroy, libnkhip), Cint, (VP,), q.ptr)
+            q.ptr = C_NULL
+        end
+        return update!(P, J)
+    end
+end
+function update!(P::HipMultigridPreconditioner, J::Ariadne.JacobianOperator)
+    check(ccall((:nk_mg_set_jacobian, libnkhip), Cint, (VP, Ref{NkProblem}, Ptr{Float64}),
+                P.ptr, problem(J.f, J.u, J.p), J.u.ptr), P.ctx, "nk_mg_set_jacobian")
+    return P
+end
+# caller-supplied coefficients: A = Σ_a k[a] δ²_a + diag(s), s a device vector or a constant
+function set_operator!(P::HipMultigridPreconditioner, k::NTuple{3, Float64}, s::Union{HipVector, Real})
+    sp, sc = s isa HipVector ? (s.ptr, 0.0) : (Ptr{Float64}(C_NULL), Float64(s))
+    check(ccall((:nk_mg_set_operator, libnkhip), Cint, (VP, Ref{NTuple{3, Float64}}, Ptr{Float64}, Float64),
+                P.ptr, Ref(k), sp, sc), P.ctx, "nk_mg_set_operator")
+    return P
+end
+function mg_levels(P::HipMultigridPreconditioner)
+    n = Ref{Int32}(0)
+    check(ccall((:nk_mg_levels, libnkhip), Cint, (VP, Ref{Int32}), P.ptr, n), P.ctx, "nk_mg_levels")
+    return Int(n[])
+end
+# z = V-cycle(v), enqueued on the context's stream
+function mg_apply!(z::HipVector, P::HipMultigridPreconditioner, v::HipVector)
+    check(ccall((:nk_mg_apply, libnkhip), Cint, (VP, Ptr{Float64}, Ptr{Float64}), P.ptr, z.ptr, v.ptr), P.ctx, "nk_mg_apply")
+    return z
+end
+# the level extents of a grid (host only)
+function mg_plan(n::NTuple{3, Int64}; max_levels = 0)
+    ext = Vector{Int64}(undef, 3 * 64)
+    nl = Ref{Int32}(0)
+    rc = ccall((:nk_mg_plan, libnkhip), Cint, (Ref{NTuple{3, Int64}}, Int32, Ptr{Int64}, Int32, Ref{Int32}),
+               Ref(n), max_levels, ext, 64, nl)
+    rc == 0 || error("nk_mg_plan: invalid argument")
+    return [Tuple(ext[3l + 1:3l + 3]) for l in 0:nl[] - 1]
+end
+nkprecond(P::HipMultigridPreconditioner) = NkPrecond(NK_PRECOND_MG, C_NULL, C_NULL, P.ptr, C_NULL, 0)
+const _mg_cache = Dict{Any, HipMultigridPreconditioner}()
+function hip_multigrid(J::Ariadne.JacobianOperator)
+    pr = problem(J.f, J.u, J.p)
+    key = (J.u.ctx, size(J.u), pr.kind, pr.hx, pr.hy, pr.hz)
+    haskey(_mg_cache, key) && return update!(_mg_cache[key], J)
+    empty!(_mg_cache)
+    return _mg_cache[key] = HipMultigridPreconditioner(J)
+end
+
 function Krylov.krylov_workspace(method::Symbol, kc::KrylovConstructor{<:HipVector}; memory::Integer = 20)
     algo = method === :gmres ? Int32(0) : method === :cg ? Int32(1) : method === :fgmres ? Int32(2) :
            error("HIP path implements :gmres, :fgmres and :cg")

@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""Time-to-solution of the multigrid-preconditioned Newton solve against the unpreconditioned one.
+
+For each grid: one Newton solve of 2D Bratu from sin_ic with N = multigrid, then the same solve without a
+preconditioner (the headline's Krylov settings: GMRES(30), restart, itmax 300, FD Jv), each timed per Newton step
+(wall clock, stream synchronised by the ||F|| every step returns).  Reports the wall time to the same ||F|| (the
+one the preconditioned solve ended at), the Newton / Krylov counts, and the per-kernel profile of ONE V-cycle
+against each kernel's byte model as a fraction of 8 TB/s.
+
+  python tools/mg_solve.py [--grids 4096x4096,16384x2048] [--out profiles/mg] [--plain-steps 50]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import _nkpath  # noqa: E402,F401
+import ariadne_hip as ah  # noqa: E402
+
+PEAK = 8.0e12  # B/s, the MI355X HBM3E peak the byte models are held against
+LAMBDA = 3.51382
+
+
+def sin_ic(nx, ny):
+    x = np.sin(np.pi * np.arange(1, nx + 1) / (nx + 1))
+    y = np.sin(np.pi * np.arange(1, ny + 1) / (ny + 1))
+    return np.ascontiguousarray(y[:, None] * x[None, :])
+
+
+def newton(ctx, nx, ny, N, max_niter, kw, memory, jv):
+    u = ah.DeviceArray.from_numpy(sin_ic(nx, ny), ctx=ctx)
+    p = (1.0 / (nx + 1), 1.0 / (ny + 1), LAMBDA)
+    hist = []
+    ctx.sync()
+    t0 = time.perf_counter()
+    _, r = ah.newton_krylov_(ah.bratu2d_, u, p, N=N, max_niter=max_niter, memory=memory, krylov_kwargs=kw, jv=jv,
+                             callback=lambda _u, _res, n_res: hist.append((time.perf_counter() - t0, n_res)))
+    ctx.sync()
+    return dict(solved=bool(r.solved), outer=r.stats.outer_iterations, inner=r.stats.inner_iterations,
+                n_matvec=r.n_matvec, n_res=r.stats.n_res, seconds=time.perf_counter() - t0,
+                history=[dict(t=t, n_res=n) for t, n in hist])
+
+
+def time_to(history, target):
+    for h in history:
+        if h["n_res"] <= target:
+            return h["t"]
+    return None
+
+
+def vcycle_profile(ctx, nx, ny):
+    u = ah.DeviceArray.from_numpy(sin_ic(nx, ny), ctx=ctx)
+    p = (1.0 / (nx + 1), 1.0 / (ny + 1), LAMBDA)
+    res = u.zero()
+    ah.bratu2d_(res, u, p)
+    J = ah.JacobianOperator(ah.bratu2d_, res, u, p)
+    mg = ah.MultigridPreconditioner(J)
+    z = u.zero()
+    for _ in range(2):  # warm
+        mg.apply(J, res, z)
+    ctx.prof_enable(1)
+    ctx.prof_reset()
+    t0 = time.perf_counter()
+    mg.apply(J, res, z)
+    wall = time.perf_counter() - t0
+    prof = ctx.prof_read()
+    ctx.prof_enable(0)
+    rows = []
+    for name, e in sorted(prof.items(), key=lambda kv: -kv[1]["ms"]):
+        if not name.startswith("mg_") or not e["timed"]:
+            continue
+        bw = e["bytes"] / (e["ms"] * 1e-3) if e["ms"] > 0 else 0.0
+        rows.append(dict(kernel=name, launches=e["launches"], ms=e["ms"], model_bytes=e["bytes"], model_gbs=bw / 1e9,
+                         fraction_of_peak=bw / PEAK))
+    levels = mg.levels
+    mg.free()
+    return dict(levels=levels, wall_ms=wall * 1e3, kernel_ms=sum(r["ms"] for r in rows), kernels=rows)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grids", default="4096x4096,16384x2048")
+    ap.add_argument("--out", default="profiles/mg")
+    ap.add_argument("--plain-steps", type=int, default=50, help="Newton steps the unpreconditioned solve may take")
+    ap.add_argument("--memory", type=int, default=30)
+    ap.add_argument("--jv", default="fd")
+    args = ap.parse_args()
+    os.makedirs(args.out, exist_ok=True)
+    ctx = ah.Context(0)
+    ah.set_default_context(ctx)
+    kw = dict(restart=True, itmax=300)
+    for N in (ah.multigrid, None):  # load every kernel before anything is timed
+        newton(ctx, 96, 80, N, 50, kw, args.memory, args.jv)
+    out = dict(settings=dict(krylov=kw, memory=args.memory, jv=args.jv, forcing="EisenstatWalker (the default)",
+                             tol="1e-6 ||F(u0)|| + 1e-12 (the default)"), grids=[])
+    lines = []
+    for g in args.grids.split(","):
+        nx, ny = (int(t) for t in g.split("x"))
+        mg = newton(ctx, nx, ny, ah.multigrid(), 50, kw, args.memory, args.jv)
+        plain = newton(ctx, nx, ny, None, args.plain_steps, kw, args.memory, args.jv)
+        target = mg["n_res"]
+        t_plain = time_to(plain["history"], target)
+        prof = vcycle_profile(ctx, nx, ny)
+        out["grids"].append(dict(grid=[nx, ny], multigrid=mg, plain=plain, target_n_res=target,
+                                 plain_seconds_to_target=t_plain, vcycle=prof))
+        lines.append(f"== 2D Bratu {nx} x {ny}, GMRES({args.memory}) restart itmax 300, {args.jv.upper()} Jv")
+        lines.append(f"  N = multigrid : solved {mg['solved']}  ||F|| {mg['n_res']:.3e}  Newton {mg['outer']}  Krylov {mg['inner']}  "
+                     f"matvecs {mg['n_matvec']}  {mg['seconds']:.4f} s")
+        reached = f"{t_plain:.4f} s" if t_plain is not None else f"not reached in {plain['outer']} Newton steps"
+        lines.append(f"  plain         : solved {plain['solved']}  ||F|| {plain['n_res']:.3e}  Newton {plain['outer']}  Krylov {plain['inner']}  "
+                     f"matvecs {plain['n_matvec']}  {plain['seconds']:.4f} s;  to ||F|| <= {target:.3e}: {reached}")
+        lines.append(f"  one V-cycle, {len(prof['levels'])} levels: kernels {prof['kernel_ms']:.3f} ms, wall {prof['wall_ms']:.3f} ms")
+        for r in prof["kernels"]:
+            lines.append(f"    {r['kernel']:<12} x{r['launches']:<3} {r['ms']:8.3f} ms  model {r['model_bytes'] / 1e6:9.1f} MB  "
+                         f"{r['model_gbs']:7.0f} GB/s  {r['fraction_of_peak']:.2f} of 8 TB/s")
+    text = "\n".join(lines)
+    print(text)
+    with open(os.path.join(args.out, "mg_solve.json"), "w") as f:
+        json.dump(out, f, indent=1)
+    with open(os.path.join(args.out, "mg_solve.txt"), "w") as f:
+        f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
