@@ -276,7 +276,8 @@ int nk_mg_set_jacobian(nk_mg* mg, const nk_problem* p, const double* u);
  * nk_newton_krylov refreshes a hierarchy from each step's u (nk_mg_set_jacobian) -- except one whose operator was
  * set here: that stays the caller's until nk_mg_set_jacobian is called on it again */
 int nk_mg_set_operator(nk_mg* mg, const double k[3], const double* s_dev, double s_const);
-/* z = V-cycle(v) */
+/* z = V-cycle(v).  z may alias v (in place): z is written only by the cycle's last launch, which reads v at the point
+ * it writes (the one-launch coarse tail has copied v into LDS before it writes z) */
 int nk_mg_apply(nk_mg* mg, double* z, const double* v);
 
 /* memory = Krylov workspace memory (GMRES restart length; default 20 like Krylov.jl). */

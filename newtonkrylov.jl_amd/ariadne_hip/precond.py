@@ -180,8 +180,6 @@ class MultigridPreconditioner(Preconditioner):
         axis, s a DeviceArray on the grid or a constant; h = the spacings (default 1 / (n + 1) per axis).  Such an
         object keeps the caller's operator: the Newton drivers do not refresh it from the Jacobian (so it also
         serves a UserResidual); call update(J) yourself to switch it to a built-in J's coefficients."""
-        import ctypes as C
-
         from .device import default_context
 
         self = cls.__new__(cls)
@@ -199,9 +197,22 @@ class MultigridPreconditioner(Preconditioner):
         prob = grid.geometry_problem()
         prob.hx, prob.hy, prob.hz = (h + [1.0, 1.0])[:3]
         self._create(ctx, grid, prob, nu, coarse_sweeps, omega, max_levels)
+        return self.set_coefficients(k, s)
+
+    def set_coefficients(self, k, s) -> "MultigridPreconditioner":
+        """Other caller-supplied coefficients on the live hierarchy (nk_mg_set_operator): k per axis, s a
+        DeviceArray on the grid or a constant, as in from_coefficients; the spacings stay.  The sign check runs
+        again, so `levels` may change."""
+        import ctypes as C
+
+        k = [float(x) for x in (k if hasattr(k, "__len__") else [k] * self.grid.dim)]
+        if len(k) != self.grid.dim:
+            raise ValueError("k: one coefficient per axis")
+        if isinstance(s, DeviceArray) and s.grid != self.grid:
+            raise ValueError("s must be a DeviceArray on `grid` (or a constant)")
         kk = (C.c_double * 3)(*(k + [0.0, 0.0])[:3])
         sd, sc = (s.ptr, 0.0) if isinstance(s, DeviceArray) else (None, float(s))
-        ctx.check(load().nk_mg_set_operator(self.handle, kk, sd, sc), "nk_mg_set_operator")
+        self.ctx.check(load().nk_mg_set_operator(self.handle, kk, sd, sc), "nk_mg_set_operator")
         self.caller_operator = True
         return self
 
@@ -217,7 +228,8 @@ class MultigridPreconditioner(Preconditioner):
         return self
 
     def vcycle(self, v: DeviceArray, z: DeviceArray | None = None) -> DeviceArray:
-        """z = V-cycle(v) (nk_mg_apply, then a sync): the preconditioner by itself, without an operator J."""
+        """z = V-cycle(v) (nk_mg_apply, then a sync): the preconditioner by itself, without an operator J.
+        z may alias v (`vcycle(v, z=v)`: in place)."""
         z = v.zero() if z is None else z
         self.ctx.check(load().nk_mg_apply(self.handle, z.ptr, v.ptr), "nk_mg_apply")
         self.ctx.sync()
