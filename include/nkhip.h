@@ -268,7 +268,8 @@ int nk_mg_plan(const int64_t n[3], int32_t max_levels, int64_t* extents, int32_t
 int nk_mg_create(nk_ctx* ctx, const nk_problem* p, const nk_mg_opts* opts, nk_mg** out);
 int nk_mg_destroy(nk_mg* mg);
 /* levels in use: nk_mg_plan's count, fewer when set-up truncated the hierarchy before a level whose
- * diagonal changes sign or vanishes */
+ * diagonal changes sign or vanishes (in SPD form, nk_mg_set_spd: also before the first level whose diagonal has
+ * the other sign than level 0's) */
 int nk_mg_levels(nk_mg* mg, int32_t* nlevels);
 /* k and s of J(u) from the problem's kind; the level-0 diagonal is nk_jacobian_diag's.  Synchronises. */
 int nk_mg_set_jacobian(nk_mg* mg, const nk_problem* p, const double* u);
@@ -279,6 +280,18 @@ int nk_mg_set_operator(nk_mg* mg, const double k[3], const double* s_dev, double
 /* z = V-cycle(v).  z may alias v (in place): z is written only by the cycle's last launch, which reads v at the point
  * it writes (the one-launch coarse tail has copied v into LDS before it writes z) */
 int nk_mg_apply(nk_mg* mg, double* z, const double* v);
+/* The SPD form, for CG's M.  With equal pre- and post-sweeps the cycle V is symmetric (the column sums D of P are
+ * constant along an axis, so R = D^-1 P^T is a multiple of P^T) and sigma V is positive definite, sigma = the sign of
+ * the level-0 diagonal (-1 for every built-in Jacobian: they are negative definite, and CG's M is then -V like the
+ * -1 ./ diag(J) of the Jacobi M).  on != 0: nk_mg_apply gives z = sigma V(v), exactly the default result times
+ * sigma, and the hierarchy in use ends before the first level whose diagonal has the other sign than level 0's
+ * (nk_mg_levels reports that count).  A property of the hierarchy, switched at any time, before or after an
+ * operator is set: no synchronisation, allocation or set-up.  The default (0) is the plain cycle. */
+int nk_mg_set_spd(nk_mg* mg, int32_t on);
+int nk_mg_get_spd(nk_mg* mg, int32_t* on);
+/* nk_mg_apply (in the form that is set) and *vz = <v, z>, accumulated by the launch that writes z (fixed order, no
+ * atomics: two calls give the same bits; z is bit-identical to nk_mg_apply's).  Synchronises. */
+int nk_mg_apply_dot(nk_mg* mg, double* z, const double* v, double* vz);
 
 /* memory = Krylov workspace memory (GMRES restart length; default 20 like Krylov.jl). */
 int nk_workspace_create(nk_ctx* ctx, int32_t algo, const nk_problem* p, int32_t memory, nk_workspace** out);

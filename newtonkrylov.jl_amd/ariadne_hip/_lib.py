@@ -142,6 +142,9 @@ SIGNATURES = {
     "nk_mg_set_jacobian": (C.c_int, [_VP, _PP, _VP]),
     "nk_mg_set_operator": (C.c_int, [_VP, _PD, _VP, _D]),
     "nk_mg_apply": (C.c_int, [_VP, _VP, _VP]),
+    "nk_mg_set_spd": (C.c_int, [_VP, _I32]),
+    "nk_mg_get_spd": (C.c_int, [_VP, C.POINTER(_I32)]),
+    "nk_mg_apply_dot": (C.c_int, [_VP, _VP, _VP, _PD]),
     "nk_dot": (C.c_int, [_VP, _I64, _VP, _VP, _PD]),
     "nk_mgs_step": (C.c_int, [_VP, _I64, C.POINTER(_VP), _I32, _VP, _I32, _PD]),
     "nk_norm": (C.c_int, [_VP, _I64, _VP, _PD]),

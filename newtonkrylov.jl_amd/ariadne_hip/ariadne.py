@@ -331,7 +331,8 @@ def newton_krylov_native(F_: DeviceResidual, u: DeviceArray, p=None, res: Device
                          krylov_kwargs: dict | None = None, memory: int = 20, jv: str = "exact", N=None, M=None):
     """newton_krylov_ with the loop itself in libnkhip.so (nk_newton_krylov, the C/C++ callers' entry
     point).  Same arguments, same result; returns (u, Result) with the histories of ||F||.  N / M: a
-    MultigridPreconditioner or the `multigrid` factory only (the C loop refreshes it from each step's u);
+    MultigridPreconditioner or the `multigrid` factory only (the C loop refreshes it from each step's u; with
+    algo="cg", M in its SPD form: `multigrid(spd=True)`);
     the other preconditioners are built per step by Python factories, which newton_krylov_ runs."""
     from .precond import MultigridPreconditioner, _MultigridFactory, multigrid
 
@@ -346,7 +347,7 @@ def newton_krylov_native(F_: DeviceResidual, u: DeviceArray, p=None, res: Device
         if not isinstance(P, MultigridPreconditioner):
             raise TypeError(f"newton_krylov_native: {name} must be a MultigridPreconditioner or the multigrid factory "
                             "(other preconditioners: newton_krylov_)")
-        if name == "M" and str(algo).lstrip(":") == "cg":
+        if name == "M" and str(algo).lstrip(":") == "cg" and not getattr(P, "spd", False):  # CG: the SPD form only
             raise NotImplementedError("algo = :cg with M = multigrid is not supported: use :gmres")
         pcs[name] = P
     kk = dict(krylov_kwargs or {})

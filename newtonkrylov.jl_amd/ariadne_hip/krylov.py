@@ -211,7 +211,8 @@ def krylov_solve_(ws: KrylovWorkspace, J, b: DeviceArray, *, restart=False, reor
                             "UserPreconditioner, GmresPreconditioner, MultigridPreconditioner, jacobi(J), ilu0(J))")
     from .precond import MultigridPreconditioner
 
-    if ws.algo == "cg" and isinstance(M, MultigridPreconditioner):
+    # CG needs an SPD M: the V-cycle in its SPD form (MultigridPreconditioner(..., spd=True) / .spd = True) only
+    if ws.algo == "cg" and isinstance(M, MultigridPreconditioner) and not getattr(M, "spd", False):
         raise NotImplementedError("algo = :cg with M = multigrid is not supported: use :gmres or :fgmres "
                                   "(the V-cycle is applied as GMRES's N or M)")
     if ws.algo == "cg" and N is not None:

@@ -155,11 +155,17 @@ class MultigridPreconditioner(Preconditioner):
     level, weight `omega`, default 2d / (2d + 1)), per axis n -> n // 2 while n > 3 (`max_levels` = 0: until
     every axis is <= 3), rediscretised coarse operators, linear prolongation, restriction D^-1 P^T.  A fixed
     linear map: valid as N or M of gmres as well as fgmres.  Built-in stencil residuals, bc_zero_, one
-    rank; everything else raises NotImplementedError.  `update(J)` refreshes s = λ exp(u) for a new u."""
+    rank; everything else raises NotImplementedError.  `update(J)` refreshes s = λ exp(u) for a new u.
 
-    def __init__(self, J, nu: int = 2, coarse_sweeps: int = 8, omega: float | None = None, max_levels: int = 0):
+    `spd=True` (or `.spd = True` at any time) is the SPD form for CG's M: z = σ V(v) with σ the sign of the level-0
+    diagonal (-1 for the built-in Jacobians, which are negative definite: M = -V, as the Jacobi M is
+    -1 ./ diag(J)), exactly the default result times σ, on the leading levels whose diagonal has that sign."""
+
+    def __init__(self, J, nu: int = 2, coarse_sweeps: int = 8, omega: float | None = None, max_levels: int = 0,
+                 spd: bool = False):
         prob = _mg_problem(J)
         self._create(J.u.ctx, J.u.grid, prob, nu, coarse_sweeps, omega, max_levels)
+        self.spd = spd
         self.update(J)
 
     def _create(self, ctx, grid, prob, nu, coarse_sweeps, omega, max_levels):
@@ -175,7 +181,7 @@ class MultigridPreconditioner(Preconditioner):
 
     @classmethod
     def from_coefficients(cls, grid, k, s, *, h=None, ctx=None, nu: int = 2, coarse_sweeps: int = 8,
-                          omega: float | None = None, max_levels: int = 0):
+                          omega: float | None = None, max_levels: int = 0, spd: bool = False):
         """The V-cycle for A = Σ_a k[a] δ²_a(h[a]) + diag(s) on `grid` with caller-supplied coefficients: k per
         axis, s a DeviceArray on the grid or a constant; h = the spacings (default 1 / (n + 1) per axis).  Such an
         object keeps the caller's operator: the Newton drivers do not refresh it from the Jacobian (so it also
@@ -197,6 +203,7 @@ class MultigridPreconditioner(Preconditioner):
         prob = grid.geometry_problem()
         prob.hx, prob.hy, prob.hz = (h + [1.0, 1.0])[:3]
         self._create(ctx, grid, prob, nu, coarse_sweeps, omega, max_levels)
+        self.spd = spd
         return self.set_coefficients(k, s)
 
     def set_coefficients(self, k, s) -> "MultigridPreconditioner":
@@ -234,6 +241,29 @@ class MultigridPreconditioner(Preconditioner):
         self.ctx.check(load().nk_mg_apply(self.handle, z.ptr, v.ptr), "nk_mg_apply")
         self.ctx.sync()
         return z
+
+    def vcycle_dot(self, v: DeviceArray, z: DeviceArray | None = None):
+        """(z, <v, z>) with z = vcycle(v): the inner product is accumulated by the launch that writes z
+        (nk_mg_apply_dot; fixed order, so two calls give the same bits).  What CG does with M = this object."""
+        import ctypes as C
+
+        z = v.zero() if z is None else z
+        vz = C.c_double(0.0)
+        self.ctx.check(load().nk_mg_apply_dot(self.handle, z.ptr, v.ptr, C.byref(vz)), "nk_mg_apply_dot")
+        return z, vz.value
+
+    @property
+    def spd(self) -> bool:
+        """The SPD form (nk_mg_set_spd): settable at any time, no set-up is redone."""
+        import ctypes as C
+
+        on = C.c_int32(0)
+        self.ctx.check(load().nk_mg_get_spd(self.handle, C.byref(on)), "nk_mg_get_spd")
+        return bool(on.value)
+
+    @spd.setter
+    def spd(self, on: bool):
+        self.ctx.check(load().nk_mg_set_spd(self.handle, int(bool(on))), "nk_mg_set_spd")
 
     @property
     def levels(self) -> list:
@@ -316,7 +346,8 @@ def multigrid(J=None, **opts):
     hierarchy is allocated once per Newton solve and reused by every step (as gmres_preconditioner reuses its
     workspace); each step refreshes s = λ exp(u) and the level diagonals from that step's u.  A factory made by
     `multigrid(...)` keeps its hierarchy for as long as it lives (`.free()` releases it); `N=multigrid` itself
-    keeps nothing beyond the solve.  Called with an operator, `multigrid(J)` is MultigridPreconditioner(J)."""
+    keeps nothing beyond the solve.  Called with an operator, `multigrid(J)` is MultigridPreconditioner(J).
+    `M=multigrid(spd=True)` is the SPD form, CG's preconditioner (algo="cg")."""
     if J is None:
         return _MultigridFactory(opts)
     if opts:

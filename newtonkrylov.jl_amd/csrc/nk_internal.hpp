@@ -334,6 +334,10 @@ int launch_user(nk_ctx* c, const StencilIn& in, Red* red);  // nk_user.cpp
 // nk_mg.hip: a multigrid preconditioner follows the Jacobian of each Newton step (nk_mg_set_jacobian), unless its
 // operator came from the caller (nk_mg_set_operator): then it is left as it is
 int mg_refresh(nk_mg* mg, const nk_problem* p, const double* u);
+// nk_mg_apply with the partials of <v, z> left in a reduction slot by the launch that writes z (red may be null:
+// nk_mg_apply itself); no host sync.  mg_is_spd: the hierarchy is in SPD form (nk_mg_set_spd), i.e. fit to be CG's M
+int mg_apply_red(nk_mg* mg, double* z, const double* v, Red* red);
+bool mg_is_spd(const nk_mg* mg);
 // roctx range for the lifetime of a scope (shows Newton steps / Krylov solves / GMRES cycles in
 // rocprofv3 --marker-trace timelines; a no-op when no profiler is attached)
 struct Range {

@@ -550,6 +550,8 @@ int cg(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk_kry
     double *x = ws->x, *r = ws->xr, *p = ws->p, *Ap = ws->w;
     // preconditioner M (Krylov.jl cg!: z = M r, gamma = <r, z>, p = z + beta p); M = I: z === r
     const nk_precond* Mp = (o->M && o->M->kind != NK_PRECOND_NONE) ? o->M : nullptr;
+    // M = a multigrid hierarchy (in SPD form, nk_krylov_solve checked): the cycle's last launch leaves <r, z> itself
+    nk_mg* Mg = (Mp && Mp->kind == NK_PRECOND_MG) ? static_cast<nk_mg*>(Mp->data) : nullptr;
     double* zr = r;
     if (Mp) {
         NK_TRY(ws_vec(ws, &ws->mr));
@@ -558,11 +560,12 @@ int cg(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk_kry
     double unused = 0.0;
     NK_TRY(launch_fill(c, n, x, 0.0));
     NK_TRY(launch_copy(c, n, r, b));
-    if (Mp) NK_TRY(apply_precond(c, A.p, Mp, A, n, zr, r, false, &unused));
-    NK_TRY(launch_copy(c, n, p, zr));
     Red rg{};
-    if (Mp) NK_TRY(launch_dot(c, n, r, zr, &rg));
-    else NK_TRY(launch_sumsq(c, n, r, &rg));
+    if (Mg) NK_TRY(mg_apply_red(Mg, zr, r, &rg));
+    else if (Mp) NK_TRY(apply_precond(c, A.p, Mp, A, n, zr, r, false, &unused));
+    NK_TRY(launch_copy(c, n, p, zr));
+    if (!Mp) NK_TRY(launch_sumsq(c, n, r, &rg));
+    else if (!Mg) NK_TRY(launch_dot(c, n, r, zr, &rg));
     double gamma = 0.0;
     NK_TRY(host_scalar(c, rg, 0, &gamma));
     double rNorm = std::sqrt(gamma);
@@ -601,7 +604,10 @@ int cg(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk_kry
         const double alpha = gamma / pAp;
         Red rn{};
         NK_TRY(launch_cg_update(c, n, alpha, x, r, p, Ap, &rn));  // x += a p ; r -= a Ap ; <r,r>
-        if (Mp) {  // z = M r ; <r, z> (the update's <r,r> partials are not used)
+        if (Mg) {  // z = M r and <r, z> in the V-cycle's last launch
+            rn = Red{};
+            NK_TRY(mg_apply_red(Mg, zr, r, &rn));
+        } else if (Mp) {  // z = M r ; <r, z> (the update's <r,r> partials are not used)
             rn = Red{};
             NK_TRY(apply_precond(c, A.p, Mp, A, n, zr, r, false, &unused));
             NK_TRY(launch_dot(c, n, r, zr, &rn));
@@ -757,8 +763,12 @@ int nk_krylov_solve(nk_workspace* ws, const nk_problem* p, const double* u, cons
     ws->u_fused = false;
     if (ws->algo == NK_ALGO_CG && o->N && o->N->kind != NK_PRECOND_NONE)
         return fail(c, NK_E_ARG, "the device CG takes no right preconditioner (use GMRES / FGMRES)");
-    if (ws->algo == NK_ALGO_CG && o->M && o->M->kind == NK_PRECOND_MG)
-        return fail(c, NK_E_ARG, "the multigrid V-cycle as CG's M is not supported (use GMRES / FGMRES)");
+    if (ws->algo == NK_ALGO_CG && o->M && o->M->kind == NK_PRECOND_MG) {
+        if (!o->M->data) return fail(c, NK_E_ARG, "multigrid preconditioner without its hierarchy (nk_mg_create)");
+        if (!mg_is_spd(static_cast<nk_mg*>(o->M->data)))
+            return fail(c, NK_E_ARG, "the multigrid V-cycle as CG's M is not supported in its default form: CG needs an SPD M "
+                                     "(nk_mg_set_spd, or use GMRES / FGMRES)");
+    }
     int rc = (ws->algo == NK_ALGO_CG) ? cg(ws, A, b, o, st, hist, hist_cap, hist_len)
                                       : gmres(ws, p, A, b, o, st, hist, hist_cap, hist_len);
     if (rc != NK_OK && c->ilu_redo && !ws->u_fused && c->nranks == 1) {

@@ -140,6 +140,35 @@ __global__ __launch_bounds__(kBlock) void k_mg_sweep(MgLv L, double omega, doubl
                                                     const double* b, const double* __restrict__ idg) {
     NK_CHUNKED(i, L.n) xn[i] = mg_sweep_pt(L, omega, om1, x, b, idg, (int)i);
 }
+// The sweep that writes the cycle's result z: the same per-point arithmetic times sigma (+-1: exact), and with RED the
+// partials of <b, z> (b = the cycle's input v, read at the point written anyway) in a fixed order, no atomics
+template <bool RED>
+__global__ __launch_bounds__(kBlock) void k_mg_sweep0_z(int n, double omega, double sigma, double* z, const double* b,
+                                                       const double* __restrict__ idg, double* __restrict__ part, int fin) {
+    __shared__ double sh[kShN];
+    double acc = 0.0;
+    NK_CHUNKED(i, n) {
+        const double bi = b[i];
+        const double zi = sigma * mg_sweep0_pt(omega, b, idg, (int)i);
+        z[i] = zi;
+        if (RED) acc = fma(bi, zi, acc);
+    }
+    if (RED) publish(acc, part, fin, sh);
+}
+template <bool RED>
+__global__ __launch_bounds__(kBlock) void k_mg_sweep_z(MgLv L, double omega, double om1, double sigma, double* z,
+                                                      const double* __restrict__ x, const double* b, const double* __restrict__ idg,
+                                                      double* __restrict__ part, int fin) {
+    __shared__ double sh[kShN];
+    double acc = 0.0;
+    NK_CHUNKED(i, L.n) {
+        const double bi = b[i];
+        const double zi = sigma * mg_sweep_pt(L, omega, om1, x, b, idg, (int)i);
+        z[i] = zi;
+        if (RED) acc = fma(bi, zi, acc);
+    }
+    if (RED) publish(acc, part, fin, sh);
+}
 __global__ __launch_bounds__(kBlock) void k_mg_resid(MgLv L, double* __restrict__ r, const double* __restrict__ x,
                                                     const double* __restrict__ b, const double* __restrict__ dg) {
     NK_CHUNKED(i, L.n) r[i] = mg_resid_pt(L, x, b, dg, (int)i);
@@ -216,7 +245,10 @@ __device__ __forceinline__ void mg_tail_sweeps(const MgLv& L, double omega, doub
     }
 }
 
-__global__ __launch_bounds__(kMgTailThreads) void k_mg_tail(MgTail T) {
+// OUT = 0: the cycle as it is.  OUT = 1: level 0 is the tail's first level and the closing loop writes sigma x.
+// OUT = 2: that, and <b, z> from the LDS copy of b into the one partial part[0].
+template <int OUT>
+__global__ __launch_bounds__(kMgTailThreads) void k_mg_tail(MgTail T, double sigma, double* part, int fin) {
     extern __shared__ double mg_lds[];
 #define MG_XA(l) (mg_lds + T.off[l])
 #define MG_XB(l) (mg_lds + T.off[l] + T.lv[l].n)
@@ -257,7 +289,18 @@ __global__ __launch_bounds__(kMgTailThreads) void k_mg_tail(MgTail T) {
     }
     const int k0 = T.nlev == 1 ? T.cs : 2 * T.nu;
     const double* x0 = (k0 & 1) ? MG_XA(0) : MG_XB(0);
-    for (int i = threadIdx.x; i < T.lv[0].n; i += kMgTailThreads) T.x[i] = x0[i];
+    if (OUT == 0) {
+        for (int i = threadIdx.x; i < T.lv[0].n; i += kMgTailThreads) T.x[i] = x0[i];
+    } else {
+        __shared__ double sh[kShN];
+        double acc = 0.0;
+        for (int i = threadIdx.x; i < T.lv[0].n; i += kMgTailThreads) {
+            const double zi = sigma * x0[i];
+            T.x[i] = zi;
+            if (OUT == 2) acc = fma(MG_B(0)[i], zi, acc);
+        }
+        if (OUT == 2) publish<kMgTailThreads>(acc, part, fin, sh);
+    }
 #undef MG_XA
 #undef MG_XB
 #undef MG_B
@@ -291,6 +334,9 @@ struct nk_mg {
     int dim = 1;
     int nlev_alloc = 0;      // levels of the plan
     int nlev = 0;            // levels in use (set-up may truncate)
+    int nlev_spd = 0;        // ... in SPD form: it also ends before the first level whose diagonal has the other sign
+    bool spd = false;        // SPD form (nk_mg_set_spd): z = sigma V(v), sigma = the sign of the level-0 diagonal
+    double sigma = 1.0;
     int tail = 0;            // first level of the one-launch coarse tail (== nlev_alloc: none)
     int nu = 2, cs = 8;
     double omega = 0.0;
@@ -321,12 +367,46 @@ int mg_launch_sweep(nk_mg* m, int l, double* xn, const double* x, const double* 
                            m->idg[l]);
     });
 }
+// how the cycle's last launch writes z: times sigma, with the partials of <v, z> into *red when given
+struct MgOut {
+    double sigma;
+    Red* red;
+    bool plain() const { return sigma == 1.0 && !red; }
+};
+// the level-0 sweep that writes z (x == nullptr: the pointwise first sweep).  The fused reduction streams on a
+// red_blocks grid like the other reductions every block of a consumer sums (k_axpy_sumsq), 16 B/pt less than
+// mg_sweep + dot together (neither b nor z is read a second time)
+int mg_launch_sweep_z(nk_mg* m, double* z, const double* x, const double* b, const MgOut& o) {
+    const MgLv& L = m->lv[0];
+    nk_ctx* c = m->c;
+    const int g = o.red ? red_blocks(L.n) : wide_blocks(L.n);
+    int fin = 0;
+    double* part = o.red ? red_out(c, g, o.red, &fin) : nullptr;
+    const char* name = x ? (o.red ? "mg_sweep_dot" : "mg_sweep") : (o.red ? "mg_sweep0_dot" : "mg_sweep0");
+    return launch(c, name, (x ? 32.0 : 24.0) * L.n, [&] {
+        if (x && o.red)
+            hipLaunchKernelGGL(k_mg_sweep_z<true>, dim3(g), dim3(kBlock), 0, c->stream, L, m->omega, 1.0 - m->omega, o.sigma, z, x, b,
+                               m->idg[0], part, fin);
+        else if (x)
+            hipLaunchKernelGGL(k_mg_sweep_z<false>, dim3(g), dim3(kBlock), 0, c->stream, L, m->omega, 1.0 - m->omega, o.sigma, z, x, b,
+                               m->idg[0], part, fin);
+        else if (o.red)
+            hipLaunchKernelGGL(k_mg_sweep0_z<true>, dim3(g), dim3(kBlock), 0, c->stream, L.n, m->omega, o.sigma, z, b, m->idg[0], part,
+                               fin);
+        else
+            hipLaunchKernelGGL(k_mg_sweep0_z<false>, dim3(g), dim3(kBlock), 0, c->stream, L.n, m->omega, o.sigma, z, b, m->idg[0], part,
+                               fin);
+    });
+}
 // `sweeps` sweeps on level l after `done` earlier ones; the x so far is *cur (unused when done == 0), the sweeps
-// ping-pong between xa / xb and the last one writes `final` when given.  *cur = where x is afterwards.
-int mg_sweeps(nk_mg* m, int l, const double* b, int done, int sweeps, double** cur, double* final) {
+// ping-pong between xa / xb and the last one writes `final` when given (level 0: the cycle's z, written as `out`
+// says).  *cur = where x is afterwards.
+int mg_sweeps(nk_mg* m, int l, const double* b, int done, int sweeps, double** cur, double* final, const MgOut& out) {
     for (int s = 0; s < sweeps; ++s, ++done) {
-        double* dst = (final && s == sweeps - 1) ? final : (*cur == m->xa[l] ? m->xb[l] : m->xa[l]);
-        if (done == 0) NK_TRY(mg_launch_sweep0(m, l, dst, b));
+        const bool last = final && s == sweeps - 1;
+        double* dst = last ? final : (*cur == m->xa[l] ? m->xb[l] : m->xa[l]);
+        if (last && !out.plain()) NK_TRY(mg_launch_sweep_z(m, dst, done == 0 ? nullptr : *cur, b, out));
+        else if (done == 0) NK_TRY(mg_launch_sweep0(m, l, dst, b));
         else NK_TRY(mg_launch_sweep(m, l, dst, *cur, b));
         *cur = dst;
     }
@@ -383,7 +463,8 @@ int mg_setup(nk_mg* m, const double k[3], const nk_problem* jac, const double* u
     std::vector<double> part((size_t)2 * kMgMinmaxBlocks * m->nlev_alloc);
     NK_HIP(c, hipMemcpyAsync(part.data(), m->part, part.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     NK_HIP(c, hipStreamSynchronize(c->stream));
-    int ok = 0;
+    int ok = 0, ok_spd = 0;
+    bool neg0 = false;
     for (; ok < m->nlev_alloc; ++ok) {
         const int g = std::min(kMgMinmaxBlocks, wide_blocks(m->lv[ok].n));
         double lo = INFINITY, hi = -INFINITY;
@@ -392,10 +473,15 @@ int mg_setup(nk_mg* m, const double k[3], const nk_problem* jac, const double* u
             hi = std::fmax(hi, part[(size_t)2 * (kMgMinmaxBlocks * ok + b) + 1]);
         }
         if (!(lo > 0.0 || hi < 0.0) || std::isinf(lo) || std::isinf(hi)) break;
+        // the SPD form's hierarchy: the leading levels whose diagonal has level 0's sign (a mixed one is not definite)
+        if (ok == 0) neg0 = hi < 0.0;
+        if (ok_spd == ok && (hi < 0.0) == neg0) ok_spd = ok + 1;
     }
     m->ready = false;
     if (ok == 0) return fail(c, NK_E_ARG, "multigrid: the diagonal of the operator changes sign, vanishes or is not finite");
     m->nlev = ok;
+    m->nlev_spd = ok_spd;
+    m->sigma = neg0 ? -1.0 : 1.0;
     m->ready = true;
     return NK_OK;
 }
@@ -469,16 +555,16 @@ int nk_mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, nk_mg**
         for (int l = m->tail; l < m->nlev_alloc; ++l) pts += (size_t)m->lv[l].n;
         m->tail_lds = 5 * sizeof(double) * pts;
         // the same limit for every hierarchy (a per-hierarchy value could lower it under an earlier, larger tail)
-        hipError_t e = m->tail_lds <= kMgTailLds
-                           ? hipFuncSetAttribute(reinterpret_cast<const void*>(k_mg_tail), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)kMgTailLds)
-                           : hipErrorInvalidValue;
+        hipError_t e = m->tail_lds <= kMgTailLds ? hipSuccess : hipErrorInvalidValue;
+        for (const void* f : {reinterpret_cast<const void*>(k_mg_tail<0>), reinterpret_cast<const void*>(k_mg_tail<1>),
+                              reinterpret_cast<const void*>(k_mg_tail<2>)})
+            if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMgTailLds);
         if (e != hipSuccess) {
             mg_free(m);
             return fail(c, NK_E_HIP, std::string("multigrid: LDS for the coarse tail: ") + hipGetErrorString(e));
         }
     }
-    m->nlev = m->nlev_alloc;
+    m->nlev = m->nlev_spd = m->nlev_alloc;
     *out = m;
     return NK_OK;
 }
@@ -491,7 +577,19 @@ int nk_mg_destroy(nk_mg* m) {
 
 int nk_mg_levels(nk_mg* m, int32_t* nlevels) {
     if (!m || !nlevels) return NK_E_ARG;
-    *nlevels = m->nlev;
+    *nlevels = m->spd ? m->nlev_spd : m->nlev;
+    return NK_OK;
+}
+
+int nk_mg_set_spd(nk_mg* m, int32_t on) {
+    if (!m) return NK_E_ARG;
+    m->spd = on != 0;
+    return NK_OK;
+}
+
+int nk_mg_get_spd(nk_mg* m, int32_t* on) {
+    if (!m || !on) return NK_E_ARG;
+    *on = m->spd ? 1 : 0;
     return NK_OK;
 }
 
@@ -535,23 +633,23 @@ int nk::mg_refresh(nk_mg* m, const nk_problem* p, const double* u) {
     return nk_mg_set_jacobian(m, p, u);
 }
 
-extern "C" {
-
-int nk_mg_apply(nk_mg* m, double* z, const double* v) {
+// one V-cycle in the form that is set; red (optional): the partials of <v, z> from the launch that writes z
+int nk::mg_apply_red(nk_mg* m, double* z, const double* v, Red* red) {
     if (!m || !z || !v) return NK_E_ARG;
     nk_ctx* c = m->c;
     if (!m->ready) return fail(c, NK_E_STATE, "multigrid: no operator set (nk_mg_set_jacobian / nk_mg_set_operator)");
-    const int L = m->nlev;
+    const int L = m->spd ? m->nlev_spd : m->nlev;
+    const MgOut out{m->spd ? m->sigma : 1.0, red};
     const int G = std::min(m->tail, L);  // levels 0 .. G - 1 run per-level kernels, G .. L - 1 the tail launch
     double* cur[kMgMaxLevels] = {};
     // descent
     for (int l = 0; l < G; ++l) {
         const double* b = l == 0 ? v : m->b[l];
         if (l == L - 1) {  // the coarsest level, too large for the tail
-            NK_TRY(mg_sweeps(m, l, b, 0, m->cs, &cur[l], l == 0 ? z : nullptr));
+            NK_TRY(mg_sweeps(m, l, b, 0, m->cs, &cur[l], l == 0 ? z : nullptr, out));
             break;
         }
-        NK_TRY(mg_sweeps(m, l, b, 0, m->nu, &cur[l], nullptr));
+        NK_TRY(mg_sweeps(m, l, b, 0, m->nu, &cur[l], nullptr, out));
         double* r = cur[l] == m->xa[l] ? m->xb[l] : m->xa[l];
         const MgLv& Lv = m->lv[l];
         NK_TRY(launch(c, "mg_resid", 32.0 * Lv.n, [&] {
@@ -579,8 +677,14 @@ int nk_mg_apply(nk_mg* m, double* z, const double* v) {
         T.b = G == 0 ? v : m->b[G];
         T.x = G == 0 ? z : m->xa[G];
         cur[G] = T.x;
-        NK_TRY(launch(c, "mg_tail", 16.0 * pts + 16.0 * m->lv[G].n, [&] {
-            hipLaunchKernelGGL(k_mg_tail, dim3(1), dim3(kMgTailThreads), lds, c->stream, T);
+        // the tail writes z itself when level 0 is in it: times sigma, and <v, z> as its one partial
+        const int mode = (G == 0 && !out.plain()) ? (red ? 2 : 1) : 0;
+        int fin = 0;
+        double* part = mode == 2 ? red_out(c, 1, red, &fin) : nullptr;
+        NK_TRY(launch(c, mode == 2 ? "mg_tail_dot" : "mg_tail", 16.0 * pts + 16.0 * m->lv[G].n, [&] {
+            if (mode == 2) hipLaunchKernelGGL(k_mg_tail<2>, dim3(1), dim3(kMgTailThreads), lds, c->stream, T, out.sigma, part, fin);
+            else if (mode == 1) hipLaunchKernelGGL(k_mg_tail<1>, dim3(1), dim3(kMgTailThreads), lds, c->stream, T, out.sigma, part, fin);
+            else hipLaunchKernelGGL(k_mg_tail<0>, dim3(1), dim3(kMgTailThreads), lds, c->stream, T, 1.0, part, fin);
         }));
     }
     // ascent
@@ -589,8 +693,27 @@ int nk_mg_apply(nk_mg* m, double* z, const double* v) {
         NK_TRY(launch(c, "mg_prolong", 16.0 * Lf.n + 8.0 * Lc.n, [&] {
             hipLaunchKernelGGL(k_mg_prolong, dim3(wide_blocks(Lf.n)), dim3(kBlock), 0, c->stream, Lf, Lc, cur[l], cur[l + 1]);
         }));
-        NK_TRY(mg_sweeps(m, l, l == 0 ? v : m->b[l], m->nu, m->nu, &cur[l], l == 0 ? z : nullptr));
+        NK_TRY(mg_sweeps(m, l, l == 0 ? v : m->b[l], m->nu, m->nu, &cur[l], l == 0 ? z : nullptr, out));
     }
+    return NK_OK;
+}
+
+bool nk::mg_is_spd(const nk_mg* m) { return m && m->spd; }
+
+extern "C" {
+
+int nk_mg_apply(nk_mg* m, double* z, const double* v) { return mg_apply_red(m, z, v, nullptr); }
+
+int nk_mg_apply_dot(nk_mg* m, double* z, const double* v, double* vz) {
+    if (!m || !z || !v || !vz) return NK_E_ARG;
+    nk_ctx* c = m->c;
+    Red r{};
+    NK_TRY(mg_apply_red(m, z, v, &r));
+    NK_TRY(finish_reduction(c, &r));
+    NK_TRY(launch_finalize(c, r, c->scal, 0));
+    NK_HIP(c, hipMemcpyAsync(c->hpin, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    NK_TRY(nk_sync(c));
+    *vz = c->hpin[0];
     return NK_OK;
 }
 

@@ -2,8 +2,10 @@
 // 2D Bratu on an N x N grid, u0 = sin(pi x) sin(pi y), newton_krylov! with GMRES(memory) and the
 // Eisenstat-Walker forcing (src/Ariadne.jl:288-372), FD or exact Jv.  Prints one JSON line.
 //
-//   bin/bratu2d_newton [N=256] [jv=fd|exact] [memory=30] [restart=1] [--mg]
+//   bin/bratu2d_newton [N=256] [jv=fd|exact] [memory=30] [restart=1] [--mg] [--cg]
 // --mg (anywhere on the line): the geometric multigrid V-cycle as the right preconditioner N (NK_PRECOND_MG).
+// --cg: Newton-CG (examples/bratu.jl:59-63's algo = :cg) instead of GMRES; with --mg the V-cycle in its SPD form
+// (nk_mg_set_spd) is CG's M.  The JSON line then carries "algo": "cg".
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -23,10 +25,11 @@
     } while (0)
 
 int main(int argc, char** argv) {
-    bool use_mg = false;
+    bool use_mg = false, use_cg = false;
     int nargs = 1;
-    for (int i = 1; i < argc; ++i) {  // strip --mg, keep the positional arguments
+    for (int i = 1; i < argc; ++i) {  // strip --mg / --cg, keep the positional arguments
         if (std::strcmp(argv[i], "--mg") == 0) use_mg = true;
+        else if (std::strcmp(argv[i], "--cg") == 0) use_cg = true;
         else argv[nargs++] = argv[i];
     }
     argc = nargs;
@@ -63,13 +66,22 @@ int main(int argc, char** argv) {
     o.memory = memory;
     o.krylov.restart = restart;
     o.krylov.jv_mode = fd ? NK_JV_FD : NK_JV_EXACT;
+    if (use_cg) {
+        o.algo = NK_ALGO_CG;
+        o.krylov.restart = 0;  // a GMRES keyword
+    }
     nk_mg* mg = nullptr;
     nk_precond Nmg{};
     if (use_mg) {
         CHECK(ctx, nk_mg_create(ctx, &p, nullptr, &mg));  // the Newton loop refreshes it from each step's u
         Nmg.kind = NK_PRECOND_MG;
         Nmg.data = mg;
-        o.krylov.N = &Nmg;
+        if (use_cg) {
+            CHECK(ctx, nk_mg_set_spd(mg, 1));  // CG's M must be SPD: sigma V, sigma = the sign of J's diagonal
+            o.krylov.M = &Nmg;
+        } else {
+            o.krylov.N = &Nmg;
+        }
     }
     nk_newton_stats st;
     double hist[64];
@@ -81,9 +93,10 @@ int main(int argc, char** argv) {
     CHECK(ctx, nk_memcpy_d2h(ctx, host.data(), u, N * N));
     double umax = 0.0;
     for (double v : host) umax = std::fmax(umax, std::fabs(v));
-    std::printf("{\"N\": %lld, \"jv\": \"%s\", %s\"solved\": %s, \"outer\": %lld, \"inner\": %lld, \"n_matvec\": %lld, "
+    std::printf("{\"N\": %lld, \"jv\": \"%s\", %s%s\"solved\": %s, \"outer\": %lld, \"inner\": %lld, \"n_matvec\": %lld, "
                 "\"n_res\": %.17g, \"tol\": %.17g, \"u_max\": %.17g, \"seconds\": %.6f, \"n_res_history\": [",
-                (long long)N, fd ? "fd" : "exact", use_mg ? "\"mg\": true, " : "", st.solved ? "true" : "false", (long long)st.outer_iterations,
+                (long long)N, fd ? "fd" : "exact", use_mg ? "\"mg\": true, " : "", use_cg ? "\"algo\": \"cg\", " : "",
+                st.solved ? "true" : "false", (long long)st.outer_iterations,
                 (long long)st.inner_iterations, (long long)st.n_matvec, st.n_res, st.tol, umax, secs);
     for (int64_t k = 0; k < nh && k < 64; ++k) std::printf("%s%.17g", k ? ", " : "", hist[k]);
     std::printf("]}\n");

@@ -442,7 +442,8 @@ nkprecond(P::HipGmresPreconditioner) = NkPrecond(NK_PRECOND_GMRES, C_NULL, C_NUL
 
 # Geometric multigrid V-cycle for the stencil Jacobians (NK_PRECOND_MG, nkhip.h): built-in residuals,
 # bc_zero!, one rank.  `N = hip_multigrid` is a factory: one hierarchy per (context, grid, kind), refreshed
-# from each Newton step's u (nk_mg_set_jacobian).  Valid for :gmres and :fgmres, as N or M.
+# from each Newton step's u (nk_mg_set_jacobian).  Valid for :gmres and :fgmres, as N or M; and in its SPD form
+# (`spd = true` / mg_set_spd!: z = σ V(v), σ the sign of the level-0 diagonal) as M of :cg -- `M = hip_multigrid_spd`.
 const NK_PRECOND_MG = Int32(5)
 struct NkMgOpts
     nu::Int32
@@ -453,7 +454,8 @@ end
 mutable struct HipMultigridPreconditioner <: HipPreconditioner
     ptr::Ptr{Cvoid}
     ctx::Any
-    function HipMultigridPreconditioner(J::Ariadne.JacobianOperator; nu = 2, coarse_sweeps = 8, omega = 0.0, max_levels = 0)
+    function HipMultigridPreconditioner(J::Ariadne.JacobianOperator; nu = 2, coarse_sweeps = 8, omega = 0.0, max_levels = 0,
+                                        spd = false)
         out = Ref{Ptr{Cvoid}}(C_NULL)
         opts = NkMgOpts(nu, coarse_sweeps, omega, max_levels)
         check(ccall((:nk_mg_create, libnkhip), Cint, (VP, Ref{NkProblem}, Ref{NkMgOpts}, Ref{Ptr{Cvoid}}),
@@ -463,8 +465,19 @@ mutable struct HipMultigridPreconditioner <: HipPreconditioner
             q.ptr == C_NULL || ccall((:nk_mg_destroy, libnkhip), Cint, (VP,), q.ptr)
             q.ptr = C_NULL
         end
+        mg_set_spd!(P, spd)
         return update!(P, J)
     end
+end
+# the SPD form (CG's M): switched at any time, nothing is set up again
+function mg_set_spd!(P, on::Bool)
+    check(ccall((:nk_mg_set_spd, libnkhip), Cint, (VP, Int32), P.ptr, on), P.ctx, "nk_mg_set_spd")
+    return P
+end
+function mg_spd(P)
+    on = Ref{Int32}(0)
+    check(ccall((:nk_mg_get_spd, libnkhip), Cint, (VP, Ref{Int32}), P.ptr, on), P.ctx, "nk_mg_get_spd")
+    return on[] != 0
 end
 function update!(P::HipMultigridPreconditioner, J::Ariadne.JacobianOperator)
     check(ccall((:nk_mg_set_jacobian, libnkhip), Cint, (VP, Ref{NkProblem}, Ptr{Float64}),
@@ -488,6 +501,13 @@ function mg_apply!(z::HipVector, P::HipMultigridPreconditioner, v::HipVector)
     check(ccall((:nk_mg_apply, libnkhip), Cint, (VP, Ptr{Float64}, Ptr{Float64}), P.ptr, z.ptr, v.ptr), P.ctx, "nk_mg_apply")
     return z
 end
+# (z, <v, z>): the inner product comes from the launch that writes z (what cg! does with M = P); synchronises
+function mg_apply_dot!(z::HipVector, P::HipMultigridPreconditioner, v::HipVector)
+    vz = Ref{Float64}(0.0)
+    check(ccall((:nk_mg_apply_dot, libnkhip), Cint, (VP, Ptr{Float64}, Ptr{Float64}, Ref{Float64}), P.ptr, z.ptr, v.ptr, vz),
+          P.ctx, "nk_mg_apply_dot")
+    return z, vz[]
+end
 # the level extents of a grid (host only)
 function mg_plan(n::NTuple{3, Int64}; max_levels = 0)
     ext = Vector{Int64}(undef, 3 * 64)
@@ -499,13 +519,15 @@ function mg_plan(n::NTuple{3, Int64}; max_levels = 0)
 end
 nkprecond(P::HipMultigridPreconditioner) = NkPrecond(NK_PRECOND_MG, C_NULL, C_NULL, P.ptr, C_NULL, 0)
 const _mg_cache = Dict{Any, HipMultigridPreconditioner}()
-function hip_multigrid(J::Ariadne.JacobianOperator)
+function hip_multigrid(J::Ariadne.JacobianOperator; spd = false)
     pr = problem(J.f, J.u, J.p)
     key = (J.u.ctx, size(J.u), pr.kind, pr.hx, pr.hy, pr.hz)
-    haskey(_mg_cache, key) && return update!(_mg_cache[key], J)
+    haskey(_mg_cache, key) && return update!(mg_set_spd!(_mg_cache[key], spd), J)
     empty!(_mg_cache)
-    return _mg_cache[key] = HipMultigridPreconditioner(J)
+    return _mg_cache[key] = HipMultigridPreconditioner(J; spd = spd)
 end
+# the M factory of algo = :cg: newton_krylov!(F!, u, p, res; algo = :cg, M = hip_multigrid_spd)
+hip_multigrid_spd(J::Ariadne.JacobianOperator) = hip_multigrid(J; spd = true)
 
 function Krylov.krylov_workspace(method::Symbol, kc::KrylovConstructor{<:HipVector}; memory::Integer = 20)
     algo = method === :gmres ? Int32(0) : method === :cg ? Int32(1) : method === :fgmres ? Int32(2) :

@@ -8,6 +8,15 @@ one the preconditioned solve ended at), the Newton / Krylov counts, and the per-
 against each kernel's byte model as a fraction of 8 TB/s.
 
   python tools/mg_solve.py [--grids 4096x4096,16384x2048] [--out profiles/mg] [--plain-steps 50]
+
+--algo cg: Newton-CG (examples/bratu.jl:59-63's algo = :cg, exact Jv) with M = the V-cycle in its SPD form against plain
+Newton-CG; a grid given as one number is 1D Bratu (the default grids: 1000 -- BASELINE config 1 -- and bratu.jl's
+10000), a 2D grid is run with M only, next to GMRES + N = multigrid on the same grid.  Then the kernels CG's fusion
+is about, per launch from one profiled run each: the last level-0 sweep with <r, z> (mg_sweep_dot) against the plain
+level-0 sweep (mg_sweep) and dot on a one-level hierarchy of every 2D grid, and the one-launch tail with <r, z>
+(mg_tail_dot) against mg_tail and dot on every 1D grid of at most 1024 points.  Writes mg_cg_solve.{txt,json}.
+
+  python tools/mg_solve.py --algo cg [--grids 1000,10000,4096x4096] [--plain-steps 50]
 """
 import argparse
 import json
@@ -81,14 +90,123 @@ def vcycle_profile(ctx, nx, ny):
     return dict(levels=levels, wall_ms=wall * 1e3, kernel_ms=sum(r["ms"] for r in rows), kernels=rows)
 
 
+def bratu(shape):
+    """(residual, u0, p) of 1D / 2D Bratu at sin_ic"""
+    if len(shape) == 1:
+        n = shape[0]
+        return ah.bratu_, np.sin(np.pi * np.arange(1, n + 1) / (n + 1)), (1.0 / (n + 1), LAMBDA)
+    nx, ny = shape
+    return ah.bratu2d_, sin_ic(nx, ny), (1.0 / (nx + 1), 1.0 / (ny + 1), LAMBDA)
+
+
+def newton_any(ctx, shape, max_niter, **kw):
+    f, u0, p = bratu(shape)
+    u = ah.DeviceArray.from_numpy(u0, ctx=ctx)
+    ctx.sync()
+    t0 = time.perf_counter()
+    _, r = ah.newton_krylov_(f, u, p, max_niter=max_niter, **kw)
+    ctx.sync()
+    return dict(solved=bool(r.solved), outer=r.stats.outer_iterations, inner=r.stats.inner_iterations,
+                n_matvec=r.n_matvec, n_res=r.stats.n_res, seconds=time.perf_counter() - t0)
+
+
+def fusion_profile(ctx, shape, reps=20):
+    """per-launch means of the launches one PCG iteration's z = M r, <r, z> is made of, fused and not (one profiled run)"""
+    f, u0, p = bratu(shape)
+    u = ah.DeviceArray.from_numpy(u0, ctx=ctx)
+    res = u.zero()
+    f(res, u, p)
+    J = ah.JacobianOperator(f, res, u, p)
+    # 2D: one level, three sweeps -- every sweep is a level-0 sweep; 1D: the whole cycle is the one-launch tail
+    opts = dict(max_levels=1, coarse_sweeps=3) if len(shape) == 2 else {}
+    mg = ah.MultigridPreconditioner(J, spd=True, **opts)
+    z = u.zero()
+
+    def once():
+        mg.vcycle_dot(res, z)
+        if len(shape) == 1:
+            mg.vcycle(res, z)
+        ah.kdot(len(res), res, z)
+
+    once()
+    ctx.prof_enable(1)
+    ctx.prof_reset()
+    for _ in range(reps):
+        once()
+    prof = ctx.prof_read()
+    ctx.prof_enable(0)
+    mg.free()
+    rows = []
+    for name, e in sorted(prof.items()):
+        if (name.startswith("mg_") or name == "dot") and e["timed"]:
+            us = 1e3 * e["ms"] / e["timed"]
+            gbs = e["bytes"] / (e["ms"] * 1e-3) / 1e9 if e["ms"] > 0 else 0.0
+            rows.append(dict(kernel=name, timed=e["timed"], us_per_launch=us, model_bytes_per_launch=e["bytes"] / e["timed"],
+                             model_gbs=gbs))
+    return rows
+
+
+def main_cg(args):
+    os.makedirs(args.out, exist_ok=True)
+    ctx = ah.Context(0)
+    ah.set_default_context(ctx)
+    for shape in ((96,), (96, 80)):  # load every kernel before anything is timed
+        newton_any(ctx, shape, 50, algo="cg", M=ah.multigrid(spd=True))
+        newton_any(ctx, shape, 50, algo="cg")
+    newton_any(ctx, (96, 80), 50, N=ah.multigrid, memory=args.memory, krylov_kwargs=dict(restart=True, itmax=300))
+    out = dict(settings=dict(jv="exact", forcing="EisenstatWalker (the default)", tol="1e-6 ||F(u0)|| + 1e-12 (the default)",
+                             gmres=dict(restart=True, itmax=300, memory=args.memory)), grids=[])
+    lines = []
+    for g in (args.grids or "1000,10000").split(","):
+        shape = tuple(int(t) for t in g.split("x"))
+        name = f"{len(shape)}D Bratu {' x '.join(map(str, shape))}"
+        row = dict(grid=list(shape))
+        row["cg_multigrid"] = mg = newton_any(ctx, shape, 50, algo="cg", M=ah.multigrid(spd=True))
+        lines.append(f"== {name}, Newton-CG, exact Jv")
+        fmt = "  {:<24}: solved {}  ||F|| {:.3e}  Newton {}  Krylov {}  matvecs {}  {:.4f} s"
+        show = lambda tag, r: lines.append(fmt.format(tag, r["solved"], r["n_res"], r["outer"], r["inner"], r["n_matvec"],  # noqa: E731
+                                                      r["seconds"]))
+        show("cg, M = multigrid(spd)", mg)
+        if len(shape) == 1:
+            # cg!'s stopping test is on sqrt(<r, M r>), which for M ~ -J^-1 is about h / 2 times ||r|| on the smooth-free
+            # residuals of a converging Newton solve: on fine grids Krylov's default atol = sqrt(eps) is met at
+            # iteration 0 before Newton's tolerance is.  The same solve with atol = 0:
+            row["cg_multigrid_atol0"] = newton_any(ctx, shape, 50, algo="cg", M=ah.multigrid(spd=True),
+                                                   krylov_kwargs=dict(atol=0.0))
+            show("cg, M, atol = 0", row["cg_multigrid_atol0"])
+            row["cg_plain"] = newton_any(ctx, shape, args.plain_steps, algo="cg")
+            show("cg, plain", row["cg_plain"])
+        else:
+            row["gmres_multigrid"] = newton_any(ctx, shape, 50, N=ah.multigrid(), memory=args.memory,
+                                                krylov_kwargs=dict(restart=True, itmax=300))
+            show(f"gmres({args.memory}), N = multigrid", row["gmres_multigrid"])
+        if len(shape) == 2 or shape[0] <= 1024:
+            row["fusion"] = fusion_profile(ctx, shape)
+            lines.append("  per launch (HIP events), " + ("one-level hierarchy: level-0 sweeps" if len(shape) == 2 else "the one-launch tail"))
+            for r in row["fusion"]:
+                lines.append(f"    {r['kernel']:<14} x{r['timed']:<4} {r['us_per_launch']:9.2f} us  model {r['model_bytes_per_launch'] / 1e6:8.2f} MB  "
+                             f"{r['model_gbs']:7.0f} GB/s")
+        out["grids"].append(row)
+    text = "\n".join(lines)
+    print(text)
+    with open(os.path.join(args.out, "mg_cg_solve.json"), "w") as f:
+        json.dump(out, f, indent=1)
+    with open(os.path.join(args.out, "mg_cg_solve.txt"), "w") as f:
+        f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--grids", default="4096x4096,16384x2048")
+    ap.add_argument("--algo", default="gmres", choices=["gmres", "cg"])
+    ap.add_argument("--grids", default=None, help="gmres: 4096x4096,16384x2048; cg: 1000,10000 (one number: 1D Bratu)")
     ap.add_argument("--out", default="profiles/mg")
     ap.add_argument("--plain-steps", type=int, default=50, help="Newton steps the unpreconditioned solve may take")
     ap.add_argument("--memory", type=int, default=30)
     ap.add_argument("--jv", default="fd")
     args = ap.parse_args()
+    if args.algo == "cg":
+        return main_cg(args)
+    args.grids = args.grids or "4096x4096,16384x2048"
     os.makedirs(args.out, exist_ok=True)
     ctx = ah.Context(0)
     ah.set_default_context(ctx)
