@@ -266,6 +266,24 @@ typedef struct nk_mg_opts {
 int nk_mg_plan(const int64_t n[3], int32_t max_levels, int64_t* extents, int32_t cap, int32_t* nlevels);
 /* opts may be null (the defaults).  NK_E_ARG for periodic boundaries, a distributed context, NK_USER* kinds */
 int nk_mg_create(nk_ctx* ctx, const nk_problem* p, const nk_mg_opts* opts, nk_mg** out);
+/* Semicoarsening, for grids and coefficients whose couplings c_a = |k_a| / h_a^2 differ between the axes (point
+ * Jacobi with full coarsening does not damp the error that is smooth along the strong axis only).  The plan (host
+ * only, no GPU; output as nk_mg_plan): with L_a = (n_a + 1) h_a of level 0, on every level c_a = |k_a| ((n_a + 1) /
+ * L_a)^2 over the axes of more than 3 points, and an axis is halved (n / 2) when it has more than 3 points and c_a >=
+ * threshold * max c; the others stay.  It stops as nk_mg_plan does.  threshold: 0 = the default 0.5, else in (0, 1]
+ * (a tiny one gives nk_mg_plan's levels).  k: null = all ones; k and h must be finite, k non-zero and h > 0 on every
+ * axis of more than one point.  An isotropic level is coarsened on every axis, so equal couplings give nk_mg_plan. */
+int nk_mg_plan_semi(const int64_t n[3], const double h[3], const double k[3], double threshold, int32_t max_levels,
+                    int64_t* extents, int32_t cap, int32_t* nlevels);
+/* nk_mg_create on caller-given level extents (extents[3 l + a], nlevels of them; opts->max_levels is ignored: the
+ * list is the plan).  The same rejections as nk_mg_create; NK_E_ARG naming the reason when level 0 is not the
+ * problem's grid, an axis of a level is neither kept nor n / 2 of an axis of more than 3 points, a level coarsens
+ * no axis, or nlevels is not in 1 .. 32.  The transfers between two levels run the kernel instantiated for their set
+ * of coarsened axes. */
+int nk_mg_create_levels(nk_ctx* ctx, const nk_problem* p, const nk_mg_opts* opts, const int64_t* extents, int32_t nlevels,
+                        nk_mg** out);
+/* the extents of the levels in use (as nk_mg_plan writes them; *nlevels = nk_mg_levels' count) */
+int nk_mg_level_extents(nk_mg* mg, int64_t* extents, int32_t cap, int32_t* nlevels);
 int nk_mg_destroy(nk_mg* mg);
 /* levels in use: nk_mg_plan's count, fewer when set-up truncated the hierarchy before a level whose
  * diagonal changes sign or vanishes (in SPD form, nk_mg_set_spd: also before the first level whose diagonal has

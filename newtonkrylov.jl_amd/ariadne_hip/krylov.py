@@ -202,6 +202,10 @@ def krylov_solve_(ws: KrylovWorkspace, J, b: DeviceArray, *, restart=False, reor
     -- so the 2D FD stencils recompute it instead of loading it; bit-identical.)"""
     if unknown:
         raise TypeError(f"unsupported Krylov keyword(s): {sorted(unknown)}")
+    from .precond import MultigridPreconditioner, _MultigridFactory, multigrid
+
+    # the multigrid factory (`multigrid` itself or `multigrid(...)`) stands for the hierarchy of this operator
+    N, M = ((P(J) if P is multigrid or isinstance(P, _MultigridFactory) else P) for P in (N, M))
     for name, P in (("N", N), ("M", M)):
         if ldiv and P is not None and not getattr(P, "ldiv", False):
             raise NotImplementedError(f"ldiv = true: give {name} as the operator that approximates J^{{-1}} "
@@ -209,7 +213,6 @@ def krylov_solve_(ws: KrylovWorkspace, J, b: DeviceArray, *, restart=False, reor
         if P is not None and not hasattr(P, "as_c"):
             raise TypeError(f"{name} must be an ariadne_hip preconditioner (DiagonalPreconditioner, "
                             "UserPreconditioner, GmresPreconditioner, MultigridPreconditioner, jacobi(J), ilu0(J))")
-    from .precond import MultigridPreconditioner
 
     # CG needs an SPD M: the V-cycle in its SPD form (MultigridPreconditioner(..., spd=True) / .spd = True) only
     if ws.algo == "cg" and isinstance(M, MultigridPreconditioner) and not getattr(M, "spd", False):

@@ -159,35 +159,57 @@ class MultigridPreconditioner(Preconditioner):
 
     `spd=True` (or `.spd = True` at any time) is the SPD form for CG's M: z = σ V(v) with σ the sign of the level-0
     diagonal (-1 for the built-in Jacobians, which are negative definite: M = -V, as the Jacobi M is
-    -1 ./ diag(J)), exactly the default result times σ, on the leading levels whose diagonal has that sign."""
+    -1 ./ diag(J)), exactly the default result times σ, on the leading levels whose diagonal has that sign.
+
+    `coarsening="semi"`: on every level only the axes whose coupling c_a = |k_a| / h_a² is at least `threshold` (in
+    (0, 1], default 0.5) times the strongest one are halved, until the level is isotropic; then every axis is, as
+    with "full" (nk_mg_plan_semi / nk_mg_create_levels; the same smoother and transfers, and the SPD form carries
+    over).  Switch to it when the spacings of the grid differ between the axes (a non-square grid on the unit
+    square: 16384 x 2048 has c_x = 64 c_y) or, with from_coefficients, when k does: point Jacobi with full
+    coarsening does not damp the error that is smooth along the strong axis only, and the Krylov step count grows
+    with the ratio.  Where the couplings are within a factor 1 / threshold of each other both give
+    the same levels.  The default stays "full"."""
 
     def __init__(self, J, nu: int = 2, coarse_sweeps: int = 8, omega: float | None = None, max_levels: int = 0,
-                 spd: bool = False):
+                 spd: bool = False, coarsening: str = "full", threshold: float = 0.5):
         prob = _mg_problem(J)
-        self._create(J.u.ctx, J.u.grid, prob, nu, coarse_sweeps, omega, max_levels)
+        # the built-in Jacobians have the same k on every axis: the plan depends on the spacings alone
+        self._create(J.u.ctx, J.u.grid, prob, nu, coarse_sweeps, omega, max_levels, coarsening, threshold, None)
         self.spd = spd
         self.update(J)
 
-    def _create(self, ctx, grid, prob, nu, coarse_sweeps, omega, max_levels):
+    def _create(self, ctx, grid, prob, nu, coarse_sweeps, omega, max_levels, coarsening="full", threshold=0.5, k=None):
         import ctypes as C
 
+        coarsening, threshold = _mg_coarsening(coarsening, threshold)
         self.ctx, self.grid, self.handle = ctx, grid, None
         self.caller_operator = False  # True: k and s came from from_coefficients, and update(J) is not applied
+        self.coarsening, self.threshold = coarsening, threshold
         self.opts = _lib.nk_mg_opts(int(nu), int(coarse_sweeps), float(omega or 0.0), int(max_levels))
         h = C.c_void_p()
-        ctx.check(load().nk_mg_create(ctx.handle, C.byref(prob), C.byref(self.opts), C.byref(h)), "nk_mg_create")
+        if coarsening == "full":
+            ctx.check(load().nk_mg_create(ctx.handle, C.byref(prob), C.byref(self.opts), C.byref(h)), "nk_mg_create")
+        else:
+            lv = multigrid_plan(grid.shape_xyz, max_levels, coarsening="semi", h=[prob.hx, prob.hy, prob.hz][: grid.dim], k=k,
+                                threshold=threshold)
+            ext = (C.c_int64 * (3 * len(lv)))(*[n for e in lv for n in (list(e) + [1, 1])[:3]])
+            ctx.check(load().nk_mg_create_levels(ctx.handle, C.byref(prob), C.byref(self.opts), ext, len(lv), C.byref(h)),
+                      "nk_mg_create_levels")
         self.handle = h
         self._c = _lib.nk_precond(_lib.NK_PRECOND_MG, None, _lib.NK_USER_PRECOND(), h, None, 0)
 
     @classmethod
     def from_coefficients(cls, grid, k, s, *, h=None, ctx=None, nu: int = 2, coarse_sweeps: int = 8,
-                          omega: float | None = None, max_levels: int = 0, spd: bool = False):
+                          omega: float | None = None, max_levels: int = 0, spd: bool = False, coarsening: str = "full",
+                          threshold: float = 0.5):
         """The V-cycle for A = Σ_a k[a] δ²_a(h[a]) + diag(s) on `grid` with caller-supplied coefficients: k per
         axis, s a DeviceArray on the grid or a constant; h = the spacings (default 1 / (n + 1) per axis).  Such an
         object keeps the caller's operator: the Newton drivers do not refresh it from the Jacobian (so it also
-        serves a UserResidual); call update(J) yourself to switch it to a built-in J's coefficients."""
+        serves a UserResidual); call update(J) yourself to switch it to a built-in J's coefficients.
+        coarsening="semi": the plan is made from this k and h (a later set_coefficients keeps it)."""
         from .device import default_context
 
+        _mg_coarsening(coarsening, threshold)
         self = cls.__new__(cls)
         ctx = ctx or (s.ctx if isinstance(s, DeviceArray) else default_context())
         if getattr(ctx, "nranks", 1) != 1 or tuple(grid.shape_xyz) != tuple(grid.global_xyz):
@@ -202,7 +224,7 @@ class MultigridPreconditioner(Preconditioner):
             raise ValueError("s must be a DeviceArray on `grid` (or a constant)")
         prob = grid.geometry_problem()
         prob.hx, prob.hy, prob.hz = (h + [1.0, 1.0])[:3]
-        self._create(ctx, grid, prob, nu, coarse_sweeps, omega, max_levels)
+        self._create(ctx, grid, prob, nu, coarse_sweeps, omega, max_levels, coarsening, threshold, k)
         self.spd = spd
         return self.set_coefficients(k, s)
 
@@ -270,9 +292,9 @@ class MultigridPreconditioner(Preconditioner):
         """Extents (x fastest) of the levels in use, finest first."""
         import ctypes as C
 
-        n = C.c_int32(0)
-        self.ctx.check(load().nk_mg_levels(self.handle, C.byref(n)), "nk_mg_levels")
-        return multigrid_plan(self.grid.shape_xyz, self.opts.max_levels)[: n.value]
+        ext, n = (C.c_int64 * (3 * 64))(), C.c_int32(0)
+        self.ctx.check(load().nk_mg_level_extents(self.handle, ext, 64, C.byref(n)), "nk_mg_level_extents")
+        return [tuple(int(ext[3 * l + a]) for a in range(self.grid.dim)) for l in range(min(n.value, 64))]
 
     def as_c(self):
         return self._c
@@ -306,14 +328,35 @@ def _mg_problem(J):
     return prob
 
 
-def multigrid_plan(shape_xyz, max_levels: int = 0) -> list:
-    """The level extents nk_mg_plan gives for a grid (host only, no GPU): [(nx[, ny[, nz]]), ...]."""
+def _mg_coarsening(coarsening, threshold):
+    """(coarsening, threshold) checked on the host: ValueError for an unknown name or a threshold outside (0, 1]"""
+    if coarsening not in ("full", "semi"):
+        raise ValueError(f'multigrid: coarsening must be "full" or "semi", not {coarsening!r}')
+    threshold = float(threshold)
+    if not 0.0 < threshold <= 1.0:
+        raise ValueError(f"multigrid: threshold must lie in (0, 1], not {threshold!r}")
+    return coarsening, threshold
+
+
+def multigrid_plan(shape_xyz, max_levels: int = 0, *, coarsening: str = "full", h=None, k=None, threshold: float = 0.5) -> list:
+    """The level extents of a grid (host only, no GPU): [(nx[, ny[, nz]]), ...].  coarsening="full": nk_mg_plan.
+    "semi": nk_mg_plan_semi with the spacings h (default 1 / (n + 1) per axis), the coefficients k per axis
+    (default all ones) and the threshold (MultigridPreconditioner)."""
     import ctypes as C
 
+    coarsening, threshold = _mg_coarsening(coarsening, threshold)
     dim = len(shape_xyz)
     n = (C.c_int64 * 3)(*(list(shape_xyz) + [1, 1])[:3])
     ext = (C.c_int64 * (3 * 64))()
     nl = C.c_int32(0)
+    if coarsening == "semi":
+        hh = [float(x) for x in (h if h is not None else [1.0 / (m + 1) for m in shape_xyz])]
+        kk = [float(x) for x in (k if k is not None else [1.0] * dim)]
+        if len(hh) != dim or len(kk) != dim:
+            raise ValueError("h, k: one value per axis")
+        _lib.check(load().nk_mg_plan_semi(n, (C.c_double * 3)(*(hh + [1.0, 1.0])[:3]), (C.c_double * 3)(*(kk + [1.0, 1.0])[:3]),
+                                          threshold, int(max_levels), ext, 64, C.byref(nl)), None, "nk_mg_plan_semi")
+        return [tuple(int(ext[3 * l + a]) for a in range(dim)) for l in range(min(nl.value, 64))]
     _lib.check(load().nk_mg_plan(n, int(max_levels), ext, 64, C.byref(nl)), None, "nk_mg_plan")
     return [tuple(int(ext[3 * l + a]) for a in range(dim)) for l in range(min(nl.value, 64))]
 
@@ -347,8 +390,10 @@ def multigrid(J=None, **opts):
     workspace); each step refreshes s = λ exp(u) and the level diagonals from that step's u.  A factory made by
     `multigrid(...)` keeps its hierarchy for as long as it lives (`.free()` releases it); `N=multigrid` itself
     keeps nothing beyond the solve.  Called with an operator, `multigrid(J)` is MultigridPreconditioner(J).
-    `M=multigrid(spd=True)` is the SPD form, CG's preconditioner (algo="cg")."""
+    `M=multigrid(spd=True)` is the SPD form, CG's preconditioner (algo="cg"); `N=multigrid(coarsening="semi")` the
+    semicoarsened hierarchy for grids whose spacings differ between the axes (MultigridPreconditioner)."""
     if J is None:
+        _mg_coarsening(opts.get("coarsening", "full"), opts.get("threshold", 0.5))
         return _MultigridFactory(opts)
     if opts:
         raise TypeError("multigrid(J, ...) with options: use MultigridPreconditioner(J, ...) or N=multigrid(...)")

@@ -4,11 +4,16 @@
 // non-nested grids n_{l+1} = n_l / 2, linear prolongation P, restriction R = D^-1 P^T as a gather (no
 // atomics: every application is bit-identical).  The per-point arithmetic lives in device functions on
 // plain pointers, shared by the per-level kernels (global memory) and the coarse tail (k_mg_tail: every
-// level of at most kMgTailPoints points, all of them in one work-group's LDS, one launch).  DESIGN.md §10.
+// level of at most kMgTailPoints points, all of them in one work-group's LDS, one launch).  The level extents are a
+// plan: mg_plan halves every axis of more than 3 points, mg_plan_semi only the strongly coupled ones (anisotropic
+// grids and coefficients), nk_mg_create_levels takes any such list; the transfers between two levels that coarsen a
+// proper subset of the axes run kernels instantiated on that subset (k_mg_restrict_m / k_mg_prolong_m).  DESIGN.md §10.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #include "nk_device.hpp"
@@ -65,12 +70,14 @@ __device__ __forceinline__ double mg_resid_pt(const MgLv& L, const double* x, co
 struct MgAx {
     int lo, cnt, w[4], D;
 };
-__device__ __forceinline__ MgAx mg_rax(int nf, int nc, int j) {
+// I: the integer type of the products, which reach n_f^2 / 2: 64-bit in general (an axis may have more than 65534
+// points), 32-bit where the launcher has checked that they fit (the same integers either way)
+template <typename I>
+__device__ __forceinline__ MgAx mg_rax_t(int nf, int nc, int j) {
     MgAx a{j, 1, {1, 0, 0, 0}, 1};
     if (nf == nc) return a;
-    // the products reach n_f^2 / 2: 64-bit (an axis may have more than 65534 points)
-    const int64_t J = j + 1, F = nf + 1, Cc = nc + 1;
-    int64_t lo = ((J - 1) * F) / Cc + 1, hi = ((J + 1) * F - 1) / Cc;
+    const I J = j + 1, F = nf + 1, Cc = nc + 1;
+    I lo = ((J - 1) * F) / Cc + 1, hi = ((J + 1) * F - 1) / Cc;
     lo = lo < 1 ? 1 : lo;
     hi = hi > nf ? nf : hi;
     hi = hi > lo + 3 ? lo + 3 : hi;  // the open interval has length 2 (n_f + 1) / (n_c + 1) <= 4: at most 4 points
@@ -78,15 +85,15 @@ __device__ __forceinline__ MgAx mg_rax(int nf, int nc, int j) {
     a.cnt = (int)(hi - lo + 1);
     a.D = 0;
     for (int t = 0; t < 4; ++t) {
-        const int64_t d = (lo + t) * Cc - J * F;
+        const I d = (lo + t) * Cc - J * F;
         a.w[t] = t < a.cnt ? (int)(F - (d < 0 ? -d : d)) : 0;
         a.D += a.w[t];
     }
     return a;
 }
-__device__ __forceinline__ double mg_restrict_pt(const MgLv& Lf, const MgLv& Lc, const double* r, int j) {
-    const int jx = j % Lc.nx, t = j / Lc.nx, jy = t % Lc.ny, jz = t / Lc.ny;
-    const MgAx ax = mg_rax(Lf.nx, Lc.nx, jx), ay = mg_rax(Lf.ny, Lc.ny, jy), az = mg_rax(Lf.nz, Lc.nz, jz);
+__device__ __forceinline__ MgAx mg_rax(int nf, int nc, int j) { return mg_rax_t<int64_t>(nf, nc, j); }
+// the gather of one coarse point from its three axes, and the final division
+__device__ __forceinline__ double mg_restrict_ax(const MgLv& Lf, const MgAx& ax, const MgAx& ay, const MgAx& az, const double* r) {
     double acc = 0.0;
     for (int c = 0; c < az.cnt; ++c)
         for (int b = 0; b < ay.cnt; ++b) {
@@ -96,6 +103,10 @@ __device__ __forceinline__ double mg_restrict_pt(const MgLv& Lf, const MgLv& Lc,
         }
     return acc / ((double)az.D * (double)ay.D * (double)ax.D);
 }
+__device__ __forceinline__ double mg_restrict_pt(const MgLv& Lf, const MgLv& Lc, const double* r, int j) {
+    const int jx = j % Lc.nx, t = j / Lc.nx, jy = t % Lc.ny, jz = t / Lc.ny;
+    return mg_restrict_ax(Lf, mg_rax(Lf.nx, Lc.nx, jx), mg_rax(Lf.ny, Lc.ny, jy), mg_rax(Lf.nz, Lc.nz, jz), r);
+}
 
 // one axis of P for fine point i (0-based): coarse points j - 1 and j (0-based; outside 0 .. n_c - 1: the
 // boundary, 0) with weights 1 - w and w, w = (q mod (n_f + 1)) / (n_f + 1), q = (i + 1) (n_c + 1), j = q / (n_f + 1)
@@ -103,31 +114,41 @@ struct MgPx {
     int j;
     double w;
 };
-__device__ __forceinline__ MgPx mg_pax(int nf, int nc, int i) {
+template <typename I>
+__device__ __forceinline__ MgPx mg_pax_t(int nf, int nc, int i) {
     if (nf == nc) return MgPx{i + 1, 0.0};
-    const int64_t q = (int64_t)(i + 1) * (nc + 1), F = nf + 1;  // 64-bit: q reaches n_f^2 / 2
+    const I q = (I)(i + 1) * (nc + 1), F = nf + 1;  // q reaches n_f^2 / 2 (I as in mg_rax_t)
     return MgPx{(int)(q / F), (double)(q % F) / (double)F};
 }
-__device__ __forceinline__ double mg_prolong_pt(const MgLv& Lf, const MgLv& Lc, const double* e, int i) {
-    const int ix = i % Lf.nx, t = i / Lf.nx, iy = t % Lf.ny, iz = t / Lf.ny;
-    const MgPx px = mg_pax(Lf.nx, Lc.nx, ix), py = mg_pax(Lf.ny, Lc.ny, iy), pz = mg_pax(Lf.nz, Lc.nz, iz);
-    double vz[2];
-    for (int c = 0; c < 2; ++c) {
+__device__ __forceinline__ MgPx mg_pax(int nf, int nc, int i) { return mg_pax_t<int64_t>(nf, nc, i); }
+// the interpolation of one fine point from its three axes.  MASK (bit a: axis a is coarsened) = 7 is the general form,
+// in which an axis that was not coarsened is the identity through its weights 1 and 0; an axis outside MASK is known
+// to be the identity, and its zero-weight neighbour is neither read nor added: the same value (a term 0 * e of a
+// finite e only decides the sign of a zero result)
+template <int MASK>
+__device__ __forceinline__ double mg_prolong_ax(const MgLv& Lc, const MgPx& px, const MgPx& py, const MgPx& pz, const double* e) {
+    constexpr bool CX = (MASK & 1) != 0, CY = (MASK & 2) != 0, CZ = (MASK & 4) != 0;
+    double vz[2] = {0.0, 0.0};
+    for (int c = 0; c < (CZ ? 2 : 1); ++c) {
         const int jz = pz.j - 1 + c;
-        double vy[2];
-        for (int b = 0; b < 2; ++b) {
+        double vy[2] = {0.0, 0.0};
+        for (int b = 0; b < (CY ? 2 : 1); ++b) {
             const int jy = py.j - 1 + b;
             double lo = 0.0, hi = 0.0;
             if (jz >= 0 && jz < Lc.nz && jy >= 0 && jy < Lc.ny) {
                 const int row = (jz * Lc.ny + jy) * Lc.nx;
                 if (px.j - 1 >= 0) lo = e[row + px.j - 1];
-                if (px.j < Lc.nx) hi = e[row + px.j];
+                if (CX && px.j < Lc.nx) hi = e[row + px.j];
             }
-            vy[b] = (1.0 - px.w) * lo + px.w * hi;
+            vy[b] = CX ? (1.0 - px.w) * lo + px.w * hi : lo;
         }
-        vz[c] = (1.0 - py.w) * vy[0] + py.w * vy[1];
+        vz[c] = CY ? (1.0 - py.w) * vy[0] + py.w * vy[1] : vy[0];
     }
-    return (1.0 - pz.w) * vz[0] + pz.w * vz[1];
+    return CZ ? (1.0 - pz.w) * vz[0] + pz.w * vz[1] : vz[0];
+}
+__device__ __forceinline__ double mg_prolong_pt(const MgLv& Lf, const MgLv& Lc, const double* e, int i) {
+    const int ix = i % Lf.nx, t = i / Lf.nx, iy = t % Lf.ny, iz = t / Lf.ny;
+    return mg_prolong_ax<7>(Lc, mg_pax(Lf.nx, Lc.nx, ix), mg_pax(Lf.ny, Lc.ny, iy), mg_pax(Lf.nz, Lc.nz, iz), e);
 }
 
 // ------------------------------------------------------------------------------ per-level kernels
@@ -178,6 +199,44 @@ __global__ __launch_bounds__(kBlock) void k_mg_restrict(MgLv Lf, MgLv Lc, double
 }
 __global__ __launch_bounds__(kBlock) void k_mg_prolong(MgLv Lf, MgLv Lc, double* __restrict__ x, const double* __restrict__ e) {
     NK_CHUNKED(i, Lf.n) x[i] = x[i] + mg_prolong_pt(Lf, Lc, e, (int)i);
+}
+// The transfers between two levels of a semicoarsened plan, instantiated on the set MASK of coarsened axes (a proper
+// subset of the used axes; all of them is the kernel above).  The block is 2^lbx points of a grid row by
+// kBlock >> lbx rows: a thread keeps its x index, so the x axis' weights are computed once and then reused down the
+// rows it walks, a wave reads and writes whole contiguous row segments (x coarsened: up to four contiguous fine
+// points per coarse point; y or z coarsened: two to four whole rows), and the axes outside MASK cost no index
+// arithmetic at all.  Per point the same device functions, fma order and final division as the general kernels.
+// S32: the index products fit 32 bits.
+template <int MASK, bool S32>
+__global__ __launch_bounds__(kBlock) void k_mg_restrict_m(MgLv Lf, MgLv Lc, int lbx, double* __restrict__ bc,
+                                                         const double* __restrict__ r) {
+    using I = typename std::conditional<S32, int32_t, int64_t>::type;
+    const int jx = (int)(blockIdx.x << lbx) + (int)(threadIdx.x & ((1u << lbx) - 1));
+    if (jx >= Lc.nx) return;
+    const MgAx ax = (MASK & 1) ? mg_rax_t<I>(Lf.nx, Lc.nx, jx) : MgAx{jx, 1, {1, 0, 0, 0}, 1};
+    const int64_t rows = (int64_t)Lc.ny * Lc.nz, rpb = kBlock >> lbx;
+    for (int64_t row = blockIdx.y * rpb + (threadIdx.x >> lbx); row < rows; row += gridDim.y * rpb) {
+        const int jy = (int)(row % Lc.ny), jz = (int)(row / Lc.ny);
+        const MgAx ay = (MASK & 2) ? mg_rax_t<I>(Lf.ny, Lc.ny, jy) : MgAx{jy, 1, {1, 0, 0, 0}, 1};
+        const MgAx az = (MASK & 4) ? mg_rax_t<I>(Lf.nz, Lc.nz, jz) : MgAx{jz, 1, {1, 0, 0, 0}, 1};
+        bc[row * Lc.nx + jx] = mg_restrict_ax(Lf, ax, ay, az, r);
+    }
+}
+template <int MASK, bool S32>
+__global__ __launch_bounds__(kBlock) void k_mg_prolong_m(MgLv Lf, MgLv Lc, int lbx, double* __restrict__ x,
+                                                        const double* __restrict__ e) {
+    using I = typename std::conditional<S32, int32_t, int64_t>::type;
+    const int ix = (int)(blockIdx.x << lbx) + (int)(threadIdx.x & ((1u << lbx) - 1));
+    if (ix >= Lf.nx) return;
+    const MgPx px = (MASK & 1) ? mg_pax_t<I>(Lf.nx, Lc.nx, ix) : MgPx{ix + 1, 0.0};
+    const int64_t rows = (int64_t)Lf.ny * Lf.nz, rpb = kBlock >> lbx;
+    for (int64_t row = blockIdx.y * rpb + (threadIdx.x >> lbx); row < rows; row += gridDim.y * rpb) {
+        const int iy = (int)(row % Lf.ny), iz = (int)(row / Lf.ny);
+        const MgPx py = (MASK & 2) ? mg_pax_t<I>(Lf.ny, Lc.ny, iy) : MgPx{iy + 1, 0.0};
+        const MgPx pz = (MASK & 4) ? mg_pax_t<I>(Lf.nz, Lc.nz, iz) : MgPx{iz + 1, 0.0};
+        const int64_t i = row * Lf.nx + ix;
+        x[i] = x[i] + mg_prolong_ax<MASK>(Lc, px, py, pz, e);
+    }
 }
 // set-up: diag = dsum + s (dsum = Σ_a -2 c_a, summed in axis order on the host) and 1 / diag
 __global__ __launch_bounds__(kBlock) void k_mg_diag(int n, double dsum, const double* __restrict__ s, double* __restrict__ dg,
@@ -323,6 +382,35 @@ int mg_plan(const int64_t n0[3], int max_levels, int64_t (*ext)[3]) {
     return L;
 }
 
+// host: the semicoarsened plan.  On every level only the axes whose coupling c_a = |k_a| / h_a² is at least tau times
+// the strongest one are halved (point Jacobi smooths the error along those; the weakly coupled axes wait until the
+// level is isotropic).  Double precision, in this order (the tests restate it): L_a = (n_a^0 + 1) h_a^0,
+// c_a = |k_a| ((n_a + 1) / L_a)² over the axes of more than 3 points.  The axis of c_max always qualifies, so every
+// level at least halves its points.
+int mg_plan_semi(const int64_t n0[3], const double h[3], const double k[3], double tau, int max_levels, int64_t (*ext)[3]) {
+    int64_t n[3] = {n0[0], n0[1], n0[2]};
+    double len[3];
+    for (int a = 0; a < 3; ++a) len[a] = (double)(n0[a] + 1) * h[a];
+    int L = 0;
+    for (;;) {
+        for (int a = 0; a < 3; ++a) ext[L][a] = n[a];
+        ++L;
+        if (L == kMgMaxLevels || (max_levels > 0 && L >= max_levels)) break;
+        if (n[0] <= 3 && n[1] <= 3 && n[2] <= 3) break;
+        double cc[3] = {0.0, 0.0, 0.0}, cmax = 0.0;
+        for (int a = 0; a < 3; ++a)
+            if (n[a] > 3) {
+                const double q = (double)(n[a] + 1) / len[a];
+                cc[a] = std::fabs(k[a]) * (q * q);
+                cmax = std::fmax(cmax, cc[a]);
+            }
+        const double bar = tau * cmax;
+        for (int a = 0; a < 3; ++a)
+            if (n[a] > 3 && cc[a] >= bar) n[a] /= 2;
+    }
+    return L;
+}
+
 }  // namespace
 }  // namespace nk
 
@@ -413,10 +501,98 @@ int mg_sweeps(nk_mg* m, int l, const double* b, int done, int sweeps, double** c
     return NK_OK;
 }
 
-int mg_restrict(nk_mg* m, int l, double* bc, const double* r, const char* name) {
+// Which transfer kernels a level pair runs.  mask = the coarsened axes when they are a proper subset of the used ones
+// (a semicoarsened level: the k_mg_*_m instantiation of that mask), 0 = the general kernels (every used axis
+// coarsened, today's levels).  The names of the profiler classes carry the mask: mg_restrict_x, mg_prolong_yz, ...
+struct MgXfer {
+    int mask;
+    bool s32;
+    bool general;  // the kernel-variant bench build forces the general kernels under the mask's class name
+};
+MgXfer mg_xfer(const nk_mg* m, int l) {
+    // the kernel-variant bench build can force the general kernels, to time both on the same level pair
+    static const bool generic = NK_TUNE("NK_MG_GENERIC", 0) != 0;
     const MgLv &Lf = m->lv[l], &Lc = m->lv[l + 1];
-    return launch(m->c, name, 8.0 * Lf.n + 8.0 * Lc.n, [&] {
-        hipLaunchKernelGGL(k_mg_restrict, dim3(wide_blocks(Lc.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, bc, r);
+    const int nf[3] = {Lf.nx, Lf.ny, Lf.nz}, nc[3] = {Lc.nx, Lc.ny, Lc.nz};
+    int mask = 0, used = 0;
+    bool s32 = true;
+    for (int a = 0; a < 3; ++a) {
+        if (nf[a] > 1) used |= 1 << a;
+        if (nf[a] != nc[a]) {
+            mask |= 1 << a;
+            s32 = s32 && (int64_t)(nf[a] + 4) * (nc[a] + 2) < ((int64_t)1 << 31);
+        }
+    }
+    // axes of at most 3 points that stay as they are while every other one is coarsened: also today's levels
+    bool rest_small = true;
+    for (int a = 0; a < 3; ++a)
+        if (nf[a] == nc[a] && nf[a] > 3) rest_small = false;
+    if (mask == 0 || mask == used || rest_small) return MgXfer{0, false, true};
+    return MgXfer{mask, s32, generic};
+}
+const char* const kMgRestrictName[7] = {"mg_restrict",    "mg_restrict_x",  "mg_restrict_y", "mg_restrict_xy",
+                                        "mg_restrict_z",  "mg_restrict_xz", "mg_restrict_yz"};
+const char* const kMgSetupName[7] = {"mg_setup_restrict",    "mg_setup_restrict_x",  "mg_setup_restrict_y", "mg_setup_restrict_xy",
+                                     "mg_setup_restrict_z",  "mg_setup_restrict_xz", "mg_setup_restrict_yz"};
+const char* const kMgProlongName[7] = {"mg_prolong",   "mg_prolong_x",  "mg_prolong_y", "mg_prolong_xy",
+                                       "mg_prolong_z", "mg_prolong_xz", "mg_prolong_yz"};
+// grid of the row-shaped kernels for rows of nx points: 2^lbx = the block's extent along x (4 .. 64, the smallest
+// that covers a short row), about eight rows per thread, at most kRedCap - 2 blocks as the streaming kernels
+struct MgRows {
+    dim3 grid;
+    int lbx;
+};
+MgRows mg_rows(int nx, int64_t rows) {
+    int lbx = 6;
+    while (lbx > 2 && (1 << (lbx - 1)) >= nx) --lbx;
+    const int64_t gx = ((int64_t)nx + (1 << lbx) - 1) >> lbx, rpb = kBlock >> lbx;
+    int64_t gy = (rows + 8 * rpb - 1) / (8 * rpb);
+    gy = std::min<int64_t>(gy, std::max<int64_t>(1, (kRedCap - 2) / gx));
+    gy = std::min<int64_t>(gy, 65535);
+    return MgRows{dim3((unsigned)gx, (unsigned)gy), lbx};
+}
+template <int MASK>
+void mg_restrict_m(nk_mg* m, const MgLv& Lf, const MgLv& Lc, bool s32, double* bc, const double* r) {
+    const MgRows g = mg_rows(Lc.nx, (int64_t)Lc.ny * Lc.nz);
+    if (s32) hipLaunchKernelGGL((k_mg_restrict_m<MASK, true>), g.grid, dim3(kBlock), 0, m->c->stream, Lf, Lc, g.lbx, bc, r);
+    else hipLaunchKernelGGL((k_mg_restrict_m<MASK, false>), g.grid, dim3(kBlock), 0, m->c->stream, Lf, Lc, g.lbx, bc, r);
+}
+template <int MASK>
+void mg_prolong_m(nk_mg* m, const MgLv& Lf, const MgLv& Lc, bool s32, double* x, const double* e) {
+    const MgRows g = mg_rows(Lf.nx, (int64_t)Lf.ny * Lf.nz);
+    if (s32) hipLaunchKernelGGL((k_mg_prolong_m<MASK, true>), g.grid, dim3(kBlock), 0, m->c->stream, Lf, Lc, g.lbx, x, e);
+    else hipLaunchKernelGGL((k_mg_prolong_m<MASK, false>), g.grid, dim3(kBlock), 0, m->c->stream, Lf, Lc, g.lbx, x, e);
+}
+
+// setup: the restriction of s during set-up (a profiler class of its own)
+int mg_restrict(nk_mg* m, int l, double* bc, const double* r, bool setup) {
+    const MgLv &Lf = m->lv[l], &Lc = m->lv[l + 1];
+    const MgXfer t = mg_xfer(m, l);
+    return launch(m->c, (setup ? kMgSetupName : kMgRestrictName)[t.mask], 8.0 * Lf.n + 8.0 * Lc.n, [&] {
+        switch (t.general ? 0 : t.mask) {
+            case 1: mg_restrict_m<1>(m, Lf, Lc, t.s32, bc, r); break;
+            case 2: mg_restrict_m<2>(m, Lf, Lc, t.s32, bc, r); break;
+            case 3: mg_restrict_m<3>(m, Lf, Lc, t.s32, bc, r); break;
+            case 4: mg_restrict_m<4>(m, Lf, Lc, t.s32, bc, r); break;
+            case 5: mg_restrict_m<5>(m, Lf, Lc, t.s32, bc, r); break;
+            case 6: mg_restrict_m<6>(m, Lf, Lc, t.s32, bc, r); break;
+            default: hipLaunchKernelGGL(k_mg_restrict, dim3(wide_blocks(Lc.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, bc, r);
+        }
+    });
+}
+int mg_prolong(nk_mg* m, int l, double* x, const double* e) {
+    const MgLv &Lf = m->lv[l], &Lc = m->lv[l + 1];
+    const MgXfer t = mg_xfer(m, l);
+    return launch(m->c, kMgProlongName[t.mask], 16.0 * Lf.n + 8.0 * Lc.n, [&] {
+        switch (t.general ? 0 : t.mask) {
+            case 1: mg_prolong_m<1>(m, Lf, Lc, t.s32, x, e); break;
+            case 2: mg_prolong_m<2>(m, Lf, Lc, t.s32, x, e); break;
+            case 3: mg_prolong_m<3>(m, Lf, Lc, t.s32, x, e); break;
+            case 4: mg_prolong_m<4>(m, Lf, Lc, t.s32, x, e); break;
+            case 5: mg_prolong_m<5>(m, Lf, Lc, t.s32, x, e); break;
+            case 6: mg_prolong_m<6>(m, Lf, Lc, t.s32, x, e); break;
+            default: hipLaunchKernelGGL(k_mg_prolong, dim3(wide_blocks(Lf.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, x, e);
+        }
     });
 }
 
@@ -445,7 +621,7 @@ int mg_setup(nk_mg* m, const double k[3], const nk_problem* jac, const double* u
             dsum = a == 0 ? -2.0 * cc[a] : dsum + -2.0 * cc[a];
         }
         L.cx = cc[0]; L.cy = cc[1]; L.cz = cc[2];
-        if (l > 0) NK_TRY(mg_restrict(m, l - 1, m->s[l], m->s[l - 1], "mg_setup_restrict"));
+        if (l > 0) NK_TRY(mg_restrict(m, l - 1, m->s[l], m->s[l - 1], true));
         if (l == 0 && jac) {
             NK_TRY(launch_jdiag(c, jac, m->dg[0], u, 0));
             NK_TRY(launch_jdiag(c, jac, m->idg[0], u, 1));
@@ -500,7 +676,31 @@ int nk_mg_plan(const int64_t n[3], int32_t max_levels, int64_t* extents, int32_t
     return NK_OK;
 }
 
-int nk_mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, nk_mg** out) {
+int nk_mg_plan_semi(const int64_t n[3], const double h[3], const double k[3], double threshold, int32_t max_levels,
+                    int64_t* extents, int32_t cap, int32_t* nlevels) {
+    if (!n || !h || !nlevels || n[0] < 1 || n[1] < 1 || n[2] < 1 || max_levels < 0 || cap < 0 || (cap > 0 && !extents)) return NK_E_ARG;
+    if (!(threshold == 0.0 || (threshold > 0.0 && threshold <= 1.0))) return NK_E_ARG;
+    double kk[3] = {1.0, 1.0, 1.0};
+    for (int a = 0; a < 3; ++a) {
+        if (n[a] == 1) continue;  // an unused axis: neither h nor k is read
+        if (k) kk[a] = k[a];
+        if (!std::isfinite(kk[a]) || kk[a] == 0.0 || !std::isfinite(h[a]) || !(h[a] > 0.0)) return NK_E_ARG;
+    }
+    const double hh[3] = {n[0] == 1 ? 1.0 : h[0], n[1] == 1 ? 1.0 : h[1], n[2] == 1 ? 1.0 : h[2]};
+    int64_t ext[kMgMaxLevels][3];
+    const int L = mg_plan_semi(n, hh, kk, threshold == 0.0 ? 0.5 : threshold, max_levels, ext);
+    for (int l = 0; l < L && l < cap; ++l)
+        for (int a = 0; a < 3; ++a) extents[3 * l + a] = ext[l][a];
+    *nlevels = L;
+    return NK_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the hierarchy on the level extents `given` (nlevels of them; validated here), or on mg_plan's when null
+int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int64_t* given, int32_t nlevels, nk_mg** out) {
     if (!c || !p || !out) return NK_E_ARG;
     if (nk_is_user(p->kind) || !mg_kind_ok(p->kind))
         return fail(c, NK_E_ARG, "multigrid: built-in stencil kinds only (a user residual's coefficients are unknown; "
@@ -514,6 +714,34 @@ int nk_mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, nk_mg**
     const double omega = opts && opts->omega != 0.0 ? opts->omega : 2.0 * g.dim / (2.0 * g.dim + 1.0);
     if (nu < 1 || cs < 1 || !(omega > 0.0) || (opts && opts->max_levels < 0))
         return fail(c, NK_E_ARG, "multigrid: nu >= 1, coarse_sweeps >= 1, omega > 0, max_levels >= 0");
+    const int64_t n0[3] = {p->nx, p->ny, p->nz};
+    const double h[3] = {p->hx, p->hy, p->hz};
+    int64_t ext[kMgMaxLevels][3];
+    int nlev = 0;
+    if (given) {
+        if (nlevels < 1 || nlevels > kMgMaxLevels) return fail(c, NK_E_ARG, "multigrid: the level list has fewer than 1 or more than 32 levels");
+        for (int a = 0; a < 3; ++a)
+            if (given[a] != n0[a]) return fail(c, NK_E_ARG, "multigrid: level 0 of the level list is not the problem's grid");
+        for (int l = 0; l < nlevels; ++l) {
+            bool coarsened = false;
+            for (int a = 0; a < 3; ++a) {
+                const int64_t v = given[3 * l + a];
+                ext[l][a] = v;
+                if (l == 0) continue;
+                const int64_t f = given[3 * (l - 1) + a];
+                if (v == f) continue;
+                if (!(f > 3 && v == f / 2))
+                    return fail(c, NK_E_ARG, "multigrid: level " + std::to_string(l) + " of the level list: an axis is neither kept nor "
+                                             "n / 2 of an axis of more than 3 points");
+                coarsened = true;
+            }
+            if (l > 0 && !coarsened)
+                return fail(c, NK_E_ARG, "multigrid: level " + std::to_string(l) + " of the level list coarsens no axis");
+        }
+        nlev = nlevels;
+    } else {
+        nlev = mg_plan(n0, opts ? opts->max_levels : 0, ext);
+    }
     nk_mg* m = new nk_mg();
     m->c = c;
     m->prob = *p;
@@ -521,10 +749,7 @@ int nk_mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, nk_mg**
     m->nu = nu;
     m->cs = cs;
     m->omega = omega;
-    const int64_t n0[3] = {p->nx, p->ny, p->nz};
-    const double h[3] = {p->hx, p->hy, p->hz};
-    int64_t ext[kMgMaxLevels][3];
-    m->nlev_alloc = mg_plan(n0, opts ? opts->max_levels : 0, ext);
+    m->nlev_alloc = nlev;
     for (int a = 0; a < 3; ++a) {
         m->h0[a] = h[a];
         m->len[a] = (double)(n0[a] + 1) * h[a];
@@ -566,6 +791,32 @@ int nk_mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, nk_mg**
     }
     m->nlev = m->nlev_spd = m->nlev_alloc;
     *out = m;
+    return NK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nk_mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, nk_mg** out) {
+    return mg_create(c, p, opts, nullptr, 0, out);
+}
+
+int nk_mg_create_levels(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int64_t* extents, int32_t nlevels,
+                        nk_mg** out) {
+    if (!extents) return NK_E_ARG;
+    return mg_create(c, p, opts, extents, nlevels, out);
+}
+
+int nk_mg_level_extents(nk_mg* m, int64_t* extents, int32_t cap, int32_t* nlevels) {
+    if (!m || !nlevels || cap < 0 || (cap > 0 && !extents)) return NK_E_ARG;
+    const int L = m->spd ? m->nlev_spd : m->nlev;
+    for (int l = 0; l < L && l < cap; ++l) {
+        extents[3 * l] = m->lv[l].nx;
+        extents[3 * l + 1] = m->lv[l].ny;
+        extents[3 * l + 2] = m->lv[l].nz;
+    }
+    *nlevels = L;
     return NK_OK;
 }
 
@@ -655,7 +906,7 @@ int nk::mg_apply_red(nk_mg* m, double* z, const double* v, Red* red) {
         NK_TRY(launch(c, "mg_resid", 32.0 * Lv.n, [&] {
             hipLaunchKernelGGL(k_mg_resid, dim3(wide_blocks(Lv.n)), dim3(kBlock), 0, c->stream, Lv, r, cur[l], b, m->dg[l]);
         }));
-        NK_TRY(mg_restrict(m, l, m->b[l + 1], r, "mg_restrict"));
+        NK_TRY(mg_restrict(m, l, m->b[l + 1], r, false));
     }
     if (G < L) {
         MgTail T{};
@@ -689,10 +940,7 @@ int nk::mg_apply_red(nk_mg* m, double* z, const double* v, Red* red) {
     }
     // ascent
     for (int l = std::min(G, L - 1) - 1; l >= 0; --l) {
-        const MgLv &Lf = m->lv[l], &Lc = m->lv[l + 1];
-        NK_TRY(launch(c, "mg_prolong", 16.0 * Lf.n + 8.0 * Lc.n, [&] {
-            hipLaunchKernelGGL(k_mg_prolong, dim3(wide_blocks(Lf.n)), dim3(kBlock), 0, c->stream, Lf, Lc, cur[l], cur[l + 1]);
-        }));
+        NK_TRY(mg_prolong(m, l, cur[l], cur[l + 1]));
         NK_TRY(mg_sweeps(m, l, l == 0 ? v : m->b[l], m->nu, m->nu, &cur[l], l == 0 ? z : nullptr, out));
     }
     return NK_OK;

@@ -455,11 +455,22 @@ mutable struct HipMultigridPreconditioner <: HipPreconditioner
     ptr::Ptr{Cvoid}
     ctx::Any
     function HipMultigridPreconditioner(J::Ariadne.JacobianOperator; nu = 2, coarse_sweeps = 8, omega = 0.0, max_levels = 0,
-                                        spd = false)
+                                        coarsening = :full, threshold = 0.5, spd = false)
+        coarsening in (:full, :semi) || throw(ArgumentError("coarsening must be :full or :semi"))
+        0.0 < threshold <= 1.0 || throw(ArgumentError("threshold must lie in (0, 1]"))
         out = Ref{Ptr{Cvoid}}(C_NULL)
         opts = NkMgOpts(nu, coarse_sweeps, omega, max_levels)
-        check(ccall((:nk_mg_create, libnkhip), Cint, (VP, Ref{NkProblem}, Ref{NkMgOpts}, Ref{Ptr{Cvoid}}),
-                    J.u.ctx.ptr, problem(J.f, J.u, J.p), opts, out), J.u.ctx, "nk_mg_create")
+        pr = problem(J.f, J.u, J.p)
+        if coarsening === :semi  # the built-in Jacobians have one k for every axis: the plan follows the spacings
+            lv = mg_plan_semi((Int64(pr.nx), Int64(pr.ny), Int64(pr.nz)), (pr.hx, pr.hy, pr.hz); threshold = threshold,
+                              max_levels = max_levels)
+            ext = Int64[n for e in lv for n in e]
+            check(ccall((:nk_mg_create_levels, libnkhip), Cint, (VP, Ref{NkProblem}, Ref{NkMgOpts}, Ptr{Int64}, Int32, Ref{Ptr{Cvoid}}),
+                        J.u.ctx.ptr, pr, opts, ext, length(lv), out), J.u.ctx, "nk_mg_create_levels")
+        else
+            check(ccall((:nk_mg_create, libnkhip), Cint, (VP, Ref{NkProblem}, Ref{NkMgOpts}, Ref{Ptr{Cvoid}}),
+                        J.u.ctx.ptr, pr, opts, out), J.u.ctx, "nk_mg_create")
+        end
         P = new(out[], J.u.ctx)
         finalizer(P) do q
             q.ptr == C_NULL || ccall((:nk_mg_destroy, libnkhip), Cint, (VP,), q.ptr)
@@ -517,14 +528,34 @@ function mg_plan(n::NTuple{3, Int64}; max_levels = 0)
     rc == 0 || error("nk_mg_plan: invalid argument")
     return [Tuple(ext[3l + 1:3l + 3]) for l in 0:nl[] - 1]
 end
+# the semicoarsened plan (host only): only the axes with c_a = |k_a| / h_a² >= threshold * max c are halved
+function mg_plan_semi(n::NTuple{3, Int64}, h::NTuple{3, Float64}; k::NTuple{3, Float64} = (1.0, 1.0, 1.0), threshold = 0.5,
+                      max_levels = 0)
+    ext = Vector{Int64}(undef, 3 * 64)
+    nl = Ref{Int32}(0)
+    rc = ccall((:nk_mg_plan_semi, libnkhip), Cint,
+               (Ref{NTuple{3, Int64}}, Ref{NTuple{3, Float64}}, Ref{NTuple{3, Float64}}, Float64, Int32, Ptr{Int64}, Int32, Ref{Int32}),
+               Ref(n), Ref(h), Ref(k), threshold, max_levels, ext, 64, nl)
+    rc == 0 || error("nk_mg_plan_semi: invalid argument")
+    return [Tuple(ext[3l + 1:3l + 3]) for l in 0:nl[] - 1]
+end
+# the extents of the levels in use
+function mg_level_extents(P::HipMultigridPreconditioner)
+    ext = Vector{Int64}(undef, 3 * 64)
+    nl = Ref{Int32}(0)
+    check(ccall((:nk_mg_level_extents, libnkhip), Cint, (VP, Ptr{Int64}, Int32, Ref{Int32}), P.ptr, ext, 64, nl), P.ctx,
+          "nk_mg_level_extents")
+    return [Tuple(ext[3l + 1:3l + 3]) for l in 0:nl[] - 1]
+end
 nkprecond(P::HipMultigridPreconditioner) = NkPrecond(NK_PRECOND_MG, C_NULL, C_NULL, P.ptr, C_NULL, 0)
 const _mg_cache = Dict{Any, HipMultigridPreconditioner}()
-function hip_multigrid(J::Ariadne.JacobianOperator; spd = false)
+# coarsening = :semi: the semicoarsened hierarchy, for grids whose spacings differ between the axes
+function hip_multigrid(J::Ariadne.JacobianOperator; spd = false, coarsening = :full, threshold = 0.5)
     pr = problem(J.f, J.u, J.p)
-    key = (J.u.ctx, size(J.u), pr.kind, pr.hx, pr.hy, pr.hz)
+    key = (J.u.ctx, size(J.u), pr.kind, pr.hx, pr.hy, pr.hz, coarsening, threshold)
     haskey(_mg_cache, key) && return update!(mg_set_spd!(_mg_cache[key], spd), J)
     empty!(_mg_cache)
-    return _mg_cache[key] = HipMultigridPreconditioner(J; spd = spd)
+    return _mg_cache[key] = HipMultigridPreconditioner(J; spd = spd, coarsening = coarsening, threshold = threshold)
 end
 # the M factory of algo = :cg: newton_krylov!(F!, u, p, res; algo = :cg, M = hip_multigrid_spd)
 hip_multigrid_spd(J::Ariadne.JacobianOperator) = hip_multigrid(J; spd = true)

@@ -9,6 +9,15 @@ against each kernel's byte model as a fraction of 8 TB/s.
 
   python tools/mg_solve.py [--grids 4096x4096,16384x2048] [--out profiles/mg] [--plain-steps 50]
 
+--coarsening semi | both: the semicoarsened hierarchy (N = multigrid(coarsening="semi")) instead of, or next to, the
+fully coarsened one in the same session; the plain solve is left out, the V-cycle's result is identified by its
+SHA-256 (equal plans must give equal bits) and the per-kernel table names the transfer kernels by their coarsened axes
+(mg_restrict_x, mg_prolong_y, ...).  Writes mg_semi_solve.{txt,json}.  --vcycle-only skips the Newton solves: with
+the kernel-variant build (NK_KBENCH_LIB=1) and NK_MG_GENERIC=1 the same level pairs run the general transfer kernels,
+so two such runs compare each instantiation with the general one.
+
+  python tools/mg_solve.py --coarsening both [--grids 16384x2048,4096x4096] [--vcycle-only] [--tag generic]
+
 --algo cg: Newton-CG (examples/bratu.jl:59-63's algo = :cg, exact Jv) with M = the V-cycle in its SPD form against plain
 Newton-CG; a grid given as one number is 1D Bratu (the default grids: 1000 -- BASELINE config 1 -- and bratu.jl's
 10000), a 2D grid is run with M only, next to GMRES + N = multigrid on the same grid.  Then the kernels CG's fusion
@@ -19,6 +28,7 @@ level-0 sweep (mg_sweep) and dot on a one-level hierarchy of every 2D grid, and 
   python tools/mg_solve.py --algo cg [--grids 1000,10000,4096x4096] [--plain-steps 50]
 """
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -40,14 +50,14 @@ def sin_ic(nx, ny):
     return np.ascontiguousarray(y[:, None] * x[None, :])
 
 
-def newton(ctx, nx, ny, N, max_niter, kw, memory, jv):
+def newton(ctx, nx, ny, N, max_niter, kw, memory, jv, workspace=None):
     u = ah.DeviceArray.from_numpy(sin_ic(nx, ny), ctx=ctx)
     p = (1.0 / (nx + 1), 1.0 / (ny + 1), LAMBDA)
     hist = []
     ctx.sync()
     t0 = time.perf_counter()
     _, r = ah.newton_krylov_(ah.bratu2d_, u, p, N=N, max_niter=max_niter, memory=memory, krylov_kwargs=kw, jv=jv,
-                             callback=lambda _u, _res, n_res: hist.append((time.perf_counter() - t0, n_res)))
+                             workspace=workspace, callback=lambda _u, _res, n_res: hist.append((time.perf_counter() - t0, n_res)))
     ctx.sync()
     return dict(solved=bool(r.solved), outer=r.stats.outer_iterations, inner=r.stats.inner_iterations,
                 n_matvec=r.n_matvec, n_res=r.stats.n_res, seconds=time.perf_counter() - t0,
@@ -61,13 +71,13 @@ def time_to(history, target):
     return None
 
 
-def vcycle_profile(ctx, nx, ny):
+def vcycle_profile(ctx, nx, ny, **opts):
     u = ah.DeviceArray.from_numpy(sin_ic(nx, ny), ctx=ctx)
     p = (1.0 / (nx + 1), 1.0 / (ny + 1), LAMBDA)
     res = u.zero()
     ah.bratu2d_(res, u, p)
     J = ah.JacobianOperator(ah.bratu2d_, res, u, p)
-    mg = ah.MultigridPreconditioner(J)
+    mg = ah.MultigridPreconditioner(J, **opts)
     z = u.zero()
     for _ in range(2):  # warm
         mg.apply(J, res, z)
@@ -87,7 +97,72 @@ def vcycle_profile(ctx, nx, ny):
                          fraction_of_peak=bw / PEAK))
     levels = mg.levels
     mg.free()
-    return dict(levels=levels, wall_ms=wall * 1e3, kernel_ms=sum(r["ms"] for r in rows), kernels=rows)
+    return dict(levels=levels, wall_ms=wall * 1e3, kernel_ms=sum(r["ms"] for r in rows), kernels=rows,
+                z_sha256=hashlib.sha256(z.to_numpy().tobytes()).hexdigest())
+
+
+def main_semi(args):
+    """full and semicoarsened hierarchies in one session (no plain solve)"""
+    os.makedirs(args.out, exist_ok=True)
+    ctx = ah.Context(0)
+    ah.set_default_context(ctx)
+    kw = dict(restart=True, itmax=300)
+    kinds = ["full", "semi"] if args.coarsening == "both" else ["semi"]
+    for c in kinds:  # load every kernel before anything is timed
+        newton(ctx, 96, 12, ah.multigrid(coarsening=c), 50, kw, args.memory, args.jv)
+    out = dict(settings=dict(krylov=kw, memory=args.memory, jv=args.jv, forcing="EisenstatWalker (the default)",
+                             tol="1e-6 ||F(u0)|| + 1e-12 (the default)", kbench_lib=os.environ.get("NK_KBENCH_LIB", ""),
+                             generic_transfers=os.environ.get("NK_MG_GENERIC", "")), grids=[])
+    lines = []
+    for g in args.grids.split(","):
+        nx, ny = (int(t) for t in g.split("x"))
+        row = dict(grid=[nx, ny])
+        lines.append(f"== 2D Bratu {nx} x {ny}, GMRES({args.memory}) restart itmax 300, {args.jv.upper()} Jv")
+        if not args.vcycle_only:
+            # "alone": a solve by itself, as mg_solve.txt times it -- the hierarchy and the Krylov workspace (memory + 1
+            # grid vectors) are allocated and freed inside the timed window.  "kept": one factory per hierarchy and one
+            # workspace for all, allocated before: the solve's own time.  The two hierarchies alternate.
+            for rep in range(2):
+                for c in kinds:
+                    r = newton(ctx, nx, ny, ah.multigrid(coarsening=c), 50, kw, args.memory, args.jv)
+                    r["protocol"] = "alone"
+                    row.setdefault(c, []).append(r)
+            facs = {c: ah.multigrid(coarsening=c) for c in kinds}
+            ws = ah.krylov_workspace("gmres", ah.KrylovConstructor(ah.DeviceArray.from_numpy(sin_ic(nx, ny), ctx=ctx), memory=args.memory))
+            for rep in range(args.reps + 1):
+                for c in kinds:
+                    r = newton(ctx, nx, ny, facs[c], 50, kw, args.memory, args.jv, workspace=ws)
+                    r["protocol"] = "kept" if rep else "kept, first (allocates the hierarchy)"
+                    row[c].append(r)
+            ws.free()
+            for c in kinds:
+                facs[c].free()
+                for r in row[c]:
+                    lines.append(f"  N = multigrid({c:<4}) {r['protocol']:<38}: solved {r['solved']}  ||F|| {r['n_res']:.3e}  "
+                                 f"Newton {r['outer']}  Krylov {r['inner']}  matvecs {r['n_matvec']}  {r['seconds']:.4f} s")
+                row[c + "_median_seconds"] = float(np.median([r["seconds"] for r in row[c] if r["protocol"] == "kept"]))
+                lines.append(f"  N = multigrid({c:<4}) median of the {args.reps} solves on the kept hierarchy and workspace: "
+                             f"{row[c + '_median_seconds']:.4f} s")
+        for c in kinds:
+            row["vcycle_" + c] = prof = vcycle_profile(ctx, nx, ny, coarsening=c)
+            lines.append(f"  one V-cycle ({c}), {len(prof['levels'])} levels {prof['levels'][:5]} ...: kernels {prof['kernel_ms']:.3f} ms, "
+                         f"wall {prof['wall_ms']:.3f} ms, sha256(z) {prof['z_sha256'][:16]}")
+            for r in prof["kernels"]:
+                lines.append(f"    {r['kernel']:<16} x{r['launches']:<3} {r['ms']:8.3f} ms  model {r['model_bytes'] / 1e6:9.1f} MB  "
+                             f"{r['model_gbs']:7.0f} GB/s  {r['fraction_of_peak']:.2f} of 8 TB/s")
+        if len(kinds) == 2:
+            same_plan = row["vcycle_full"]["levels"] == row["vcycle_semi"]["levels"]
+            same_bits = row["vcycle_full"]["z_sha256"] == row["vcycle_semi"]["z_sha256"]
+            row["same_plan"], row["same_bits"] = same_plan, same_bits
+            lines.append(f"  semi against full: the same plan {same_plan}, the same bits of z {same_bits}")
+        out["grids"].append(row)
+    text = "\n".join(lines)
+    print(text)
+    stem = os.path.join(args.out, "mg_semi_solve" + (f"_{args.tag}" if args.tag else ""))
+    with open(stem + ".json", "w") as f:
+        json.dump(out, f, indent=1)
+    with open(stem + ".txt", "w") as f:
+        f.write(text + "\n")
 
 
 def bratu(shape):
@@ -203,10 +278,16 @@ def main():
     ap.add_argument("--plain-steps", type=int, default=50, help="Newton steps the unpreconditioned solve may take")
     ap.add_argument("--memory", type=int, default=30)
     ap.add_argument("--jv", default="fd")
+    ap.add_argument("--coarsening", default="full", choices=["full", "semi", "both"])
+    ap.add_argument("--vcycle-only", action="store_true", help="--coarsening semi | both: the V-cycle profiles without the solves")
+    ap.add_argument("--reps", type=int, default=5, help="--coarsening semi | both: timed solves per hierarchy")
+    ap.add_argument("--tag", default="", help="--coarsening semi | both: suffix of the output files")
     args = ap.parse_args()
     if args.algo == "cg":
         return main_cg(args)
     args.grids = args.grids or "4096x4096,16384x2048"
+    if args.coarsening != "full":
+        return main_semi(args)
     os.makedirs(args.out, exist_ok=True)
     ctx = ah.Context(0)
     ah.set_default_context(ctx)
