@@ -424,9 +424,10 @@ typedef struct nk_prof_entry {
     double bytes_all;      /* algorithmic bytes of ALL launches (per-launch sizes may vary)   */
     double dram_bytes_all; /* the unique-DRAM model of ALL launches: each distinct operand byte once
                               (re-reads counted as Infinity-Cache hits -- a lower bound on DRAM traffic) */
-    char kernel[64];       /* stencil classes: the instantiation the last launch ran, as rocprofv3 names it
-                              without the namespace / argument list (e.g. "nk::k_st2d<7, 2, 4, 2, true, true>");
-                              empty for the other classes */
+    char kernel[64];       /* classes that dispatch among instantiations -- the stencils and the resident MGS sweep
+                              (mgs_sweep, arnoldi_step): the one the last launch ran, as rocprofv3 names it without
+                              the argument list (e.g. "nk::k_st2d<7, 2, 4, 2, true, true>",
+                              "nk::k_mgs_res<25, 8, false, false, false, 0, false, 4>"); empty for the other classes */
 } nk_prof_entry;
 /* every = 0: off; every = k > 0: time every k-th launch of each kernel class with a pair of HIP
  * events on the context stream (k > 1 keeps the event overhead out of the timed region). */

@@ -1,4 +1,4 @@
-"""GPU tests of the resident MGS sweep (launch_mgs_sweep / k_mgs_res in nk_kernels.hip).
+"""GPU tests of the resident MGS sweep (launch_mgs_sweep / k_mgs_res in nk_resident.hip).
 
 From 512^2 up, every Arnoldi step's MGS sweep runs as ONE launch with q held in registers and LDS
 (one block per CU, partial sums handed between passes as tagged granules).  These solves cover
@@ -10,7 +10,9 @@ determinism, and the in-kernel peer-mailbox reduction (one rank, self-send) bit 
 the local one; a heat time step whose sweeps are only partly resident (6144^2); and the optional
 fused FD Jv phase (NK_RES_JV=1, a child process).  The full
 residency of config 2 (4096^2) is covered by test_hip.py's
-test_bratu2d_4096_full_size and by bench.py's CPU/GPU agreement check.
+test_bratu2d_4096_full_size and by bench.py's CPU/GPU agreement check.  These shapes select 0, 16 or 89
+register slots; test_hip_resident_variants.py runs the other instantiations (25, 32, 48, 64, and 16 at
+full residency) and the sweep's pass-count limit.
 """
 import numpy as np
 import pytest
