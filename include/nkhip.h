@@ -61,6 +61,8 @@ extern "C" {
 #define NK_ALGO_GMRES 0    /* krylov_workspace(:gmres, …), src/Ariadne.jl:317-318 */
 #define NK_ALGO_CG 1       /* krylov_workspace(:cg, …)    (examples/bratu.jl:59-63) */
 #define NK_ALGO_FGMRES 2   /* krylov_workspace(:fgmres, …) (examples/bratu.jl:131-157): flexible right-preconditioned GMRES */
+#define NK_ALGO_MINRES 3   /* krylov_workspace(:minres, …): Paige-Saunders MINRES for the symmetric (possibly
+                              indefinite) stencil Jacobians, M SPD or absent, no N; `memory` is ignored */
 
 /* Right preconditioner N (Krylov.jl's `N`, ldiv = false: z = N v approximates A^{-1} v), as Krylov.jl
  * 0.10 applies it: NK_ALGO_GMRES multiplies J N V_k and updates x += N (V y) once per cycle;
@@ -227,7 +229,9 @@ typedef struct nk_krylov_opts {
     const nk_precond* M;          /* left preconditioner (null: none): Krylov.jl's `M` (ldiv = false), the
                                      `M = M(J)` Ariadne forwards (src/Ariadne.jl:327-329).  gmres!/fgmres!:
                                      r0 = M (b - A x), q = M A N V_k, the stopping test on ||M r||;
-                                     cg!: the SPD preconditioner (z = M r, gamma = <r, z>)                   */
+                                     cg!: the SPD preconditioner (z = M r, gamma = <r, z>);
+                                     minres: the SPD preconditioner (y = M r, beta = sqrt(<r, y>)), history and
+                                     stopping test in the M-norm; <r, M r> < 0 ends the solve with status 3    */
     int32_t f0_is_residual;       /* 1: F0 is exactly F(u) as nk_residual / nk_residual_norm computed it for this
                                      u and problem (the Newton loop's res): the 2D FD operator recomputes F(u)
                                      from the u it loads anyway instead of reading F0 -- bit-identical, 8 B/pt
@@ -235,7 +239,7 @@ typedef struct nk_krylov_opts {
 } nk_krylov_opts;
 
 typedef struct nk_krylov_stats {
-    int64_t niter;                /* workspace.stats.niter (Arnoldi / CG iterations)  */
+    int64_t niter;                /* workspace.stats.niter (Arnoldi / CG / Lanczos iterations) */
     int32_t solved, inconsistent, breakdown, status; /* status 1 solved 2 tired 3 breakdown 4 zero curvature */
     int64_t n_matvec;             /* mul!(J) calls incl. restart residuals            */
     double u_norm;                /* ||u|| after the fused update (opts.u_update)     */
@@ -337,7 +341,7 @@ typedef struct nk_newton_opts {
     int32_t forcing;              /* NK_FORCING_*                                              */
     double eta;                   /* Fixed η (0.1)                                             */
     double eta_max, gamma;        /* EisenstatWalker (0.999, 0.9)                              */
-    int32_t algo;                 /* NK_ALGO_GMRES / NK_ALGO_CG                                */
+    int32_t algo;                 /* NK_ALGO_GMRES / NK_ALGO_CG / NK_ALGO_FGMRES / NK_ALGO_MINRES */
     int32_t memory;               /* Krylov workspace memory (20)                              */
     nk_krylov_opts krylov;        /* krylov_kwargs; jv_mode selects the operator               */
     int32_t rtol_user;            /* krylov.rtol came from krylov_kwargs: it wins (:330-333)   */

@@ -28,7 +28,7 @@ NK_HEAT2D_MIDPOINT, NK_HEAT3D_MIDPOINT, NK_HEAT2D_TRAPEZOID, NK_HEAT3D_TRAPEZOID
 NK_USER1D, NK_USER2D, NK_USER3D = 16, 17, 18
 NK_BC_ZERO, NK_BC_PERIODIC = 0, 1
 NK_JV_EXACT, NK_JV_FD = 0, 1
-NK_ALGO_GMRES, NK_ALGO_CG, NK_ALGO_FGMRES = 0, 1, 2
+NK_ALGO_GMRES, NK_ALGO_CG, NK_ALGO_FGMRES, NK_ALGO_MINRES = 0, 1, 2, 3
 NK_PRECOND_NONE, NK_PRECOND_DIAG, NK_PRECOND_USER, NK_PRECOND_GMRES, NK_PRECOND_ILU0 = 0, 1, 2, 3, 4
 NK_PRECOND_MG = 5
 

@@ -332,7 +332,7 @@ def newton_krylov_native(F_: DeviceResidual, u: DeviceArray, p=None, res: Device
     """newton_krylov_ with the loop itself in libnkhip.so (nk_newton_krylov, the C/C++ callers' entry
     point).  Same arguments, same result; returns (u, Result) with the histories of ||F||.  N / M: a
     MultigridPreconditioner or the `multigrid` factory only (the C loop refreshes it from each step's u; with
-    algo="cg", M in its SPD form: `multigrid(spd=True)`);
+    algo="cg" or "minres", M in its SPD form: `multigrid(spd=True)`);
     the other preconditioners are built per step by Python factories, which newton_krylov_ runs."""
     from .precond import MultigridPreconditioner, _MultigridFactory, multigrid
 
@@ -349,6 +349,11 @@ def newton_krylov_native(F_: DeviceResidual, u: DeviceArray, p=None, res: Device
                             "(other preconditioners: newton_krylov_)")
         if name == "M" and str(algo).lstrip(":") == "cg" and not getattr(P, "spd", False):  # CG: the SPD form only
             raise NotImplementedError("algo = :cg with M = multigrid is not supported: use :gmres")
+        if name == "M" and str(algo).lstrip(":") == "minres" and not getattr(P, "spd", False):  # MINRES: the same
+            raise NotImplementedError("algo = :minres with M = multigrid in its default form is not supported: "
+                                      "use multigrid(spd=True), or :gmres")
+        if name == "N" and str(algo).lstrip(":") == "minres":
+            raise TypeError("minres! takes its preconditioner as M")
         pcs[name] = P
     kk = dict(krylov_kwargs or {})
     unknown = set(kk) - {"restart", "reorthogonalization", "itmax", "atol", "rtol"}
@@ -365,7 +370,13 @@ def newton_krylov_native(F_: DeviceResidual, u: DeviceArray, p=None, res: Device
         o.forcing, o.eta_max, o.gamma = _lib.NK_FORCING_EW, float(forcing.eta_max), float(forcing.gamma)
     else:
         raise TypeError("forcing must be Fixed, EisenstatWalker or None")
-    o.algo = {"gmres": _lib.NK_ALGO_GMRES, "cg": _lib.NK_ALGO_CG}[str(algo).lstrip(":")]
+    algos = {"gmres": _lib.NK_ALGO_GMRES, "cg": _lib.NK_ALGO_CG, "minres": _lib.NK_ALGO_MINRES}
+    if str(algo).lstrip(":") not in algos:
+        raise NotImplementedError(f"newton_krylov_native: algo = :{str(algo).lstrip(':')} -- :gmres, :cg and :minres "
+                                  "(others: newton_krylov_)")
+    if str(algo).lstrip(":") == "minres" and (kk.get("restart") or kk.get("reorthogonalization")):
+        raise TypeError("restart / reorthogonalization are GMRES keywords")
+    o.algo = algos[str(algo).lstrip(":")]
     o.memory = int(memory)
     o.krylov.restart = int(bool(kk.get("restart", False)))
     o.krylov.reorthogonalization = int(bool(kk.get("reorthogonalization", False)))

@@ -148,7 +148,9 @@ class KrylovStats:
 
 _STATUS = {0: "unknown", 1: "solution good enough given atol and rtol", 2: "maximum number of iterations exceeded",
            3: "breakdown", 4: "zero curvature detected"}
-_ALGOS = {"gmres": _lib.NK_ALGO_GMRES, "cg": _lib.NK_ALGO_CG, "fgmres": _lib.NK_ALGO_FGMRES}
+_ALGOS = {"gmres": _lib.NK_ALGO_GMRES, "cg": _lib.NK_ALGO_CG, "fgmres": _lib.NK_ALGO_FGMRES,
+          "minres": _lib.NK_ALGO_MINRES}
+_SYMMETRIC = ("cg", "minres")  # the short recurrences: an SPD M, no N, no GMRES keywords
 
 
 class KrylovWorkspace:
@@ -156,7 +158,7 @@ class KrylovWorkspace:
 
     def __init__(self, algo: str, kc: KrylovConstructor):
         if algo not in _ALGOS:
-            raise NotImplementedError(f"algo = :{algo} -- the HIP path implements :gmres, :fgmres and :cg "
+            raise NotImplementedError(f"algo = :{algo} -- the HIP path implements :gmres, :fgmres, :cg and :minres "
                                       "(other Krylov methods are out of scope, SURVEY.md §2 C16)")
         self.algo = algo
         self.memory = int(kc.memory)
@@ -214,13 +216,18 @@ def krylov_solve_(ws: KrylovWorkspace, J, b: DeviceArray, *, restart=False, reor
             raise TypeError(f"{name} must be an ariadne_hip preconditioner (DiagonalPreconditioner, "
                             "UserPreconditioner, GmresPreconditioner, MultigridPreconditioner, jacobi(J), ilu0(J))")
 
-    # CG needs an SPD M: the V-cycle in its SPD form (MultigridPreconditioner(..., spd=True) / .spd = True) only
+    # CG and MINRES need an SPD M: the V-cycle in its SPD form (MultigridPreconditioner(..., spd=True) / .spd = True) only
     if ws.algo == "cg" and isinstance(M, MultigridPreconditioner) and not getattr(M, "spd", False):
         raise NotImplementedError("algo = :cg with M = multigrid is not supported: use :gmres or :fgmres "
                                   "(the V-cycle is applied as GMRES's N or M)")
+    if ws.algo == "minres" and isinstance(M, MultigridPreconditioner) and not getattr(M, "spd", False):
+        raise NotImplementedError("algo = :minres with M = multigrid in its default form is not supported: MINRES "
+                                  "needs an SPD M, multigrid(spd=True) (or use :gmres / :fgmres)")
     if ws.algo == "cg" and N is not None:
         raise TypeError("cg! takes its preconditioner as M (Krylov.jl has no right preconditioner for CG)")
-    if ws.algo == "cg" and (restart or reorthogonalization):
+    if ws.algo == "minres" and N is not None:
+        raise TypeError("minres! takes its preconditioner as M (Krylov.jl has no right preconditioner for MINRES)")
+    if ws.algo in _SYMMETRIC and (restart or reorthogonalization):
         raise TypeError("restart / reorthogonalization are GMRES keywords")
     prob = J.problem()
     opts = _lib.nk_krylov_opts(int(bool(restart)), int(bool(reorthogonalization)), int(itmax), J.jv_mode,

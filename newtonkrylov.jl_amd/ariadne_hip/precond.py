@@ -390,7 +390,7 @@ def multigrid(J=None, **opts):
     workspace); each step refreshes s = λ exp(u) and the level diagonals from that step's u.  A factory made by
     `multigrid(...)` keeps its hierarchy for as long as it lives (`.free()` releases it); `N=multigrid` itself
     keeps nothing beyond the solve.  Called with an operator, `multigrid(J)` is MultigridPreconditioner(J).
-    `M=multigrid(spd=True)` is the SPD form, CG's preconditioner (algo="cg"); `N=multigrid(coarsening="semi")` the
+    `M=multigrid(spd=True)` is the SPD form, CG's and MINRES's preconditioner (algo="cg" / "minres"); `N=multigrid(coarsening="semi")` the
     semicoarsened hierarchy for grids whose spacings differ between the axes (MultigridPreconditioner)."""
     if J is None:
         _mg_coarsening(opts.get("coarsening", "full"), opts.get("threshold", 0.5))

@@ -26,6 +26,7 @@ struct MbInfo {
 };
 hipError_t resident_bind_mb(const MbInfo& m);  // nk_resident.hip's copy of g_mb
 hipError_t kernels_bind_mb(const MbInfo& m);   // nk_kernels.hip's copy
+hipError_t minres_bind_mb(const MbInfo& m);    // nk_minres.hip's copy
 // the stencil instantiation units' copies (nk_stencil_inst.hip, one per problem kind)
 hipError_t stencil_bind_mb_1(const MbInfo& m);
 hipError_t stencil_bind_mb_2(const MbInfo& m);

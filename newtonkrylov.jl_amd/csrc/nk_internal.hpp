@@ -318,6 +318,17 @@ int launch_cg_update(nk_ctx* c, int64_t n, double alpha, double* x, double* r, c
                      const double* Ap, Red* rr);
 int launch_cg_direction(nk_ctx* c, int64_t n, double beta, double* p, const double* r);
 int launch_diag_apply(nk_ctx* c, int64_t n, double* z, const double* d, const double* v, Red* red);  // z = d .* v (+ ||z||^2)
+// MINRES pieces (nk_minres.hip).  The Lanczos step after the Jv: alpha = Σ `alpha` (mirrored to alpha_host, mapped
+// host memory); t = (jv - (*beta / *oldbeta) r1) - (alpha / *beta) r2 over r1 (first: no r1 term); d (optional):
+// y = d .* t; rb (optional): the partials of <t, y> (<t, t> without d); ry (optional, with d): those of ||y||^2
+int launch_minres_lanczos(nk_ctx* c, int64_t n, const double* jv, double* r1, const double* r2, const double* d, double* y,
+                          const double* beta, const double* oldbeta, int first, Red alpha, double* alpha_host, Red* rb,
+                          Red* ry);
+// w = ((v - oldeps w1) - delta w2) / gamma over w1; x += phi w
+int launch_minres_update(nk_ctx* c, int64_t n, const double* v, double* w1, const double* w2, double* x, double oldeps,
+                         double delta, double gamma, double phi);
+// *beta_dev = sqrt(Σ rb); host[1] = Σ rb, host[2] = Σ ry (0 without ry): host is mapped host memory
+int launch_minres_scalars(nk_ctx* c, Red rb, const Red* ry, double* beta_dev, double* host);
 int launch_jdiag(nk_ctx* c, const nk_problem* p, double* out, const double* u, int recip);        // diag(J(u)) or 1 ./ diag
 int launch_ilu0_factor(nk_ctx* c, const nk_problem* p, int dim, double* d);                       // diag(J) -> D~ (in place)
 int launch_ilu0_solve(nk_ctx* c, const nk_problem* p, int dim, const double* d, double* z, const double* v);  // z = (LU)^-1 v

@@ -1,5 +1,5 @@
 // nk_krylov.cpp -- device-resident Krylov.jl 0.10 gmres!/fgmres!/cg! for the Jacobian operator, with
-// Krylov.jl's right (N) and left (M) preconditioners.
+// Krylov.jl's right (N) and left (M) preconditioners, and MINRES (minres()) for the symmetric J.
 //
 // Restates krylov_workspace(algo, KrylovConstructor(res)) + krylov_solve!(workspace, J, b; kwargs)
 // as called by Ariadne (src/Ariadne.jl:317-318, :338, :340, :367) -- SURVEY.md Appendix A.
@@ -36,9 +36,10 @@ struct nk_workspace {
     double* w2 = nullptr;  // gmres: q of even steps (the fused Jv reads q_{k-1} while writing q_k)
     double* xr = nullptr;  // gmres restart: Δx (chunked x update);  cg: r
     double* p = nullptr;   // cg: search direction
+    double* mv[4] = {nullptr, nullptr, nullptr, nullptr};  // minres: r2, v, w1, w2 (x = x, w = J v, xr = r1)
     std::vector<double*> V;
     std::vector<double*> Z;  // flexible form: Z_k = N V_k (right preconditioner)
-    double* mr = nullptr;    // left preconditioner: r0 = M w (gmres) / z = M r (cg)
+    double* mr = nullptr;    // left preconditioner: r0 = M w (gmres) / z = M r (cg) / y = M r2 (minres)
     double* mw = nullptr;    // left preconditioner: w = A N V_k before q = M w (gmres)
     double* hdev = nullptr;  // device Hessenberg columns: 2 slots of (2*cap + 2) doubles (steps k, k+1 in flight)
     double* ydev = nullptr;  // device y (cap doubles)
@@ -636,6 +637,148 @@ int cg(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk_kry
     return NK_OK;
 }
 
+// kbench knob: NK_MINRES_BLAS1=1 assembles the Lanczos step from the BLAS-1 launches (axpy, axpy, sumsq / diagonal
+// apply + dot, two host scalars per iteration) instead of k_minres_lanczos (slower)
+const int minres_blas1 = NK_TUNE("NK_MINRES_BLAS1", 0);
+
+// MINRES (Paige & Saunders 1975) for the symmetric, possibly indefinite J with an SPD M or none: the recurrence of
+// DESIGN.md §11.  Krylov.jl's minres! is not restated line by line (its further stopping tests -- ||A|| ||x||-relative,
+// the Acond limit, the windowed forward error -- are absent: parity unpinned).  Per iteration: the Jv launch (applies J
+// to y / beta with beta on the device, stores v, emits <v, Jv>), k_minres_lanczos, M where it is not the diagonal,
+// k_minres_scalars, ONE host synchronisation (alpha and beta^2 arrive together), then k_minres_update with the
+// rotation's scalars by value.
+int minres(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk_krylov_stats* st, double* hist,
+           int64_t hist_cap, int64_t* hist_len) {
+    nk_ctx* c = ws->c;
+    const int64_t n = ws->n;
+    int64_t nh = 0;
+    double *x = ws->x, *jv = ws->w, *r1 = ws->xr, *r2 = ws->mv[0], *v = ws->mv[1], *w1 = ws->mv[2], *w2 = ws->mv[3];
+    const nk_precond* Mp = (o->M && o->M->kind != NK_PRECOND_NONE) ? o->M : nullptr;
+    nk_mg* Mg = (Mp && Mp->kind == NK_PRECOND_MG) ? static_cast<nk_mg*>(Mp->data) : nullptr;
+    const double* Md = (Mp && Mp->kind == NK_PRECOND_DIAG) ? Mp->diag : nullptr;
+    if (Mp && Mp->kind == NK_PRECOND_DIAG && !Md) return fail(c, NK_E_ARG, "diagonal preconditioner without its diagonal");
+    if (Mp) NK_TRY(ws_vec(ws, &ws->mr));
+    double* y = Mp ? ws->mr : r2;  // without M, y is r2 itself
+    const bool need_yn = Mp && A.mode == NK_JV_FD;  // the FD step needs ||v||_2 = ||y||_2 / beta
+    NK_TRY(ws_scalars(ws, 1));
+    double* sc = ws->hdev;  // beta_k lives in sc[k % 3] (beta_{k-1} and beta_{k+1} beside it)
+    volatile double* hp = ws->hpin;  // mapped host scalars: [0] alpha, [1] beta^2, [2] ||y||^2
+    double unused = 0.0;
+    // y = M r (r in rsrc) with the partials of <r, y> in *rb and, where needed, of ||y||^2 in *ry
+    auto precond = [&](const double* rsrc, Red* rb, Red* ry) -> int {
+        if (!Mp) return launch_sumsq(c, n, rsrc, rb);
+        if (Mg) NK_TRY(mg_apply_red(Mg, y, rsrc, rb));
+        else {
+            NK_TRY(apply_precond(c, A.p, Mp, A, n, y, rsrc, false, &unused));
+            NK_TRY(launch_dot(c, n, rsrc, y, rb));
+        }
+        if (need_yn) NK_TRY(launch_sumsq(c, n, y, ry));
+        return NK_OK;
+    };
+    // beta_{k} = sqrt(Σ rb) to the device slot, beta^2 and ||y||^2 to the host: the iteration's one synchronisation
+    auto scalars = [&](Red rb, Red ry, int64_t k) -> int {
+        NK_TRY(finish_reduction(c, &rb));
+        if (need_yn) NK_TRY(finish_reduction(c, &ry));
+        NK_TRY(launch_minres_scalars(c, rb, need_yn ? &ry : nullptr, sc + k % 3, ws->hpin_dev));
+        NK_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->prof) prof_drain(c, false);
+        return mb_check(c);
+    };
+    NK_TRY(launch_fill(c, n, x, 0.0));
+    NK_TRY(launch_fill(c, n, w1, 0.0));
+    NK_TRY(launch_fill(c, n, w2, 0.0));
+    NK_TRY(launch_copy(c, n, r1, b));
+    NK_TRY(launch_copy(c, n, r2, b));
+    Red rb{}, ry{};
+    NK_TRY(precond(r2, &rb, &ry));
+    NK_TRY(scalars(rb, ry, 1));
+    double beta2 = hp[1], ynorm = std::sqrt(hp[2]);
+    st->inconsistent = 0;
+    st->breakdown = 0;
+    bool breakdown = beta2 < 0.0;  // <r, M r> < 0: M is not positive definite
+    const double beta1 = std::sqrt(beta2);
+    PUSH_HIST(beta1);
+    if (beta2 == 0.0 || breakdown) {
+        st->niter = 0;
+        st->solved = breakdown ? 0 : 1;
+        st->breakdown = breakdown;
+        st->status = breakdown ? 3 : 1;
+        if (hist_len) *hist_len = nh;
+        return NK_OK;
+    }
+    int64_t iter = 0, itmax = o->itmax == 0 ? 2 * n : o->itmax;
+    double oldb = 0.0, beta = beta1, dbar = 0.0, eps = 0.0, phibar = beta1, cs = -1.0, sn = 0.0;
+    const double tol = o->atol + o->rtol * beta1;
+    bool solved = phibar <= tol, tired = iter >= itmax;
+    while (!(solved || tired || breakdown)) {
+        iter++;
+        const int first = iter == 1;
+        const double* bdev = sc + iter % 3;
+        const double* odev = sc + (iter + 2) % 3;
+        Red ra{};
+        // J (y / beta), v = y / beta stored, partials of <v, J v>
+        NK_TRY(A.apply(jv, y, Mp ? ynorm / beta : 1.0, EPI_DOT, nullptr, &ra, bdev, v));
+        rb = Red{};
+        ry = Red{};
+        if (minres_blas1 && (!Mp || Md)) {
+            double alpha = 0.0;
+            NK_TRY(host_scalar(c, ra, 0, &alpha));
+            hp[0] = alpha;
+            if (!first) NK_TRY(launch_axpy(c, n, -(beta / oldb), r1, jv));
+            NK_TRY(launch_axpy(c, n, -(alpha / beta), r2, jv));
+            std::swap(jv, r1);  // t is where r1 is rotated from
+            if (Md) {
+                NK_TRY(launch_diag_apply(c, n, y, Md, r1, need_yn ? &ry : nullptr));
+                NK_TRY(launch_dot(c, n, r1, y, &rb));
+            } else {
+                NK_TRY(launch_sumsq(c, n, r1, &rb));
+            }
+        } else {
+            NK_TRY(finish_reduction(c, &ra));
+            const bool fused = !Mp || Md;  // beta^2 (and ||y||^2) from the Lanczos launch itself
+            NK_TRY(launch_minres_lanczos(c, n, jv, r1, r2, Md, Md ? y : nullptr, bdev, odev, first, ra, ws->hpin_dev,
+                                         fused ? &rb : nullptr, (fused && need_yn) ? &ry : nullptr));
+            if (!fused) NK_TRY(precond(r1, &rb, &ry));
+        }
+        NK_TRY(scalars(rb, ry, iter + 1));
+        const double alpha = hp[0];
+        beta2 = hp[1];
+        std::swap(r1, r2);  // r1 = r2; r2 = t
+        if (!Mp) y = r2;
+        if (beta2 < 0.0) {  // x stays the last completed iterate
+            breakdown = true;
+            iter--;
+            break;
+        }
+        ynorm = std::sqrt(hp[2]);
+        oldb = beta;
+        beta = std::sqrt(beta2);
+        const double oldeps = eps;
+        const double delta = cs * dbar + sn * alpha;
+        const double gbar = sn * dbar - cs * alpha;
+        eps = sn * beta;
+        dbar = -cs * beta;
+        const double gamma = std::fmax(std::sqrt(gbar * gbar + beta * beta), DBL_EPSILON);
+        cs = gbar / gamma;
+        sn = beta / gamma;
+        const double phi = cs * phibar;
+        phibar = sn * phibar;
+        // w = ((v - oldeps w1) - delta w2) / gamma over w1; x += phi w
+        NK_TRY(launch_minres_update(c, n, v, w1, w2, x, oldeps, delta, gamma, phi));
+        std::swap(w1, w2);  // w1 = w2; w2 = w
+        PUSH_HIST(phibar);
+        solved = phibar <= tol;
+        tired = iter >= itmax;
+    }
+    NK_HIP(c, hipStreamSynchronize(c->stream));
+    st->niter = iter;
+    st->solved = solved;
+    st->breakdown = breakdown;
+    st->status = solved ? 1 : (breakdown ? 3 : (tired ? 2 : 0));
+    if (hist_len) *hist_len = nh;
+    return NK_OK;
+}
+
 }  // namespace
 }  // namespace nk
 
@@ -677,7 +820,7 @@ int nk_precond_apply(nk_ctx* c, const nk_problem* p, const nk_precond* N, const 
 
 int nk_workspace_create(nk_ctx* c, int32_t algo, const nk_problem* p, int32_t memory, nk_workspace** out) {
     if (!c || !p || !out) return NK_E_ARG;
-    if (algo != NK_ALGO_GMRES && algo != NK_ALGO_CG && algo != NK_ALGO_FGMRES)
+    if (algo != NK_ALGO_GMRES && algo != NK_ALGO_CG && algo != NK_ALGO_FGMRES && algo != NK_ALGO_MINRES)
         return fail(c, NK_E_ARG, "unsupported Krylov algorithm");
     Geo g;
     NK_TRY(geometry(c, p, &g));
@@ -691,7 +834,7 @@ int nk_workspace_create(nk_ctx* c, int32_t algo, const nk_problem* p, int32_t me
     int rc = NK_OK;
     if ((rc = nk_vec_alloc(c, &ws->prob, &ws->x)) != NK_OK || (rc = nk_vec_alloc(c, &ws->prob, &ws->w)) != NK_OK ||
         (rc = nk_vec_alloc(c, &ws->prob, &ws->xr)) != NK_OK ||
-        (algo != NK_ALGO_CG && (rc = nk_vec_alloc(c, &ws->prob, &ws->w2)) != NK_OK) ||
+        (algo != NK_ALGO_CG && algo != NK_ALGO_MINRES && (rc = nk_vec_alloc(c, &ws->prob, &ws->w2)) != NK_OK) ||
         hipMalloc(&ws->bdev, 2 * sizeof(double)) != hipSuccess ||
         hipEventCreateWithFlags(&ws->col_ready[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ws->col_ready[1], hipEventDisableTiming) != hipSuccess) {
@@ -701,6 +844,13 @@ int nk_workspace_create(nk_ctx* c, int32_t algo, const nk_problem* p, int32_t me
     }
     if (algo == NK_ALGO_CG) {
         if ((rc = nk_vec_alloc(c, &ws->prob, &ws->p)) != NK_OK) {
+            nk_workspace_destroy(ws);
+            return rc;
+        }
+    } else if (algo == NK_ALGO_MINRES) {  // x, J v, r1 above; r2, v, w1, w2 here; y with the first M (`memory` is ignored)
+        for (double*& m : ws->mv)
+            if (rc == NK_OK) rc = nk_vec_alloc(c, &ws->prob, &m);
+        if (rc != NK_OK || (rc = ws_scalars(ws, 1)) != NK_OK) {
             nk_workspace_destroy(ws);
             return rc;
         }
@@ -719,7 +869,7 @@ int nk_workspace_destroy(nk_workspace* ws) {
     nk_ctx* c = ws->c;
     for (double* v : ws->V) nk_vec_free(c, v);
     for (double* v : ws->Z) nk_vec_free(c, v);
-    for (double* v : {ws->x, ws->w, ws->w2, ws->xr, ws->p, ws->mr, ws->mw})
+    for (double* v : {ws->x, ws->w, ws->w2, ws->xr, ws->p, ws->mr, ws->mw, ws->mv[0], ws->mv[1], ws->mv[2], ws->mv[3]})
         if (v) nk_vec_free(c, v);
     for (hipEvent_t e : ws->col_ready)
         if (e) (void)hipEventDestroy(e);
@@ -747,7 +897,7 @@ int nk_krylov_solve(nk_workspace* ws, const nk_problem* p, const double* u, cons
     if (g.n != ws->n) return fail(c, NK_E_ARG, "problem size does not match the workspace");
     if (o->jv_mode == NK_JV_FD && !F0) return fail(c, NK_E_ARG, "FD Jv needs F0 = F(u)");
     *st = nk_krylov_stats{};
-    Range solve_range(ws->algo == NK_ALGO_CG ? "cg_solve" : "gmres_solve");
+    Range solve_range(ws->algo == NK_ALGO_CG ? "cg_solve" : (ws->algo == NK_ALGO_MINRES ? "minres_solve" : "gmres_solve"));
     Op A{c, p, o->jv_mode, u, F0, 0.0};
     A.f0r = o->f0_is_residual != 0 && o->jv_mode == NK_JV_FD;
     NK_TRY(halo_exchange(c, p, u));  // u (and u_n) are constant during the solve: one exchange
@@ -761,16 +911,22 @@ int nk_krylov_solve(nk_workspace* ws, const nk_problem* p, const double* u, cons
         }
     }
     ws->u_fused = false;
-    if (ws->algo == NK_ALGO_CG && o->N && o->N->kind != NK_PRECOND_NONE)
-        return fail(c, NK_E_ARG, "the device CG takes no right preconditioner (use GMRES / FGMRES)");
-    if (ws->algo == NK_ALGO_CG && o->M && o->M->kind == NK_PRECOND_MG) {
+    const bool sym = ws->algo == NK_ALGO_CG || ws->algo == NK_ALGO_MINRES;  // the short recurrences: M SPD, no N
+    if (sym && o->N && o->N->kind != NK_PRECOND_NONE)
+        return fail(c, NK_E_ARG, ws->algo == NK_ALGO_CG ? "the device CG takes no right preconditioner (use GMRES / FGMRES)"
+                                                        : "the device MINRES takes no right preconditioner (use GMRES / FGMRES)");
+    if (sym && o->M && o->M->kind == NK_PRECOND_MG) {
         if (!o->M->data) return fail(c, NK_E_ARG, "multigrid preconditioner without its hierarchy (nk_mg_create)");
         if (!mg_is_spd(static_cast<nk_mg*>(o->M->data)))
             return fail(c, NK_E_ARG, "the multigrid V-cycle as CG's M is not supported in its default form: CG needs an SPD M "
                                      "(nk_mg_set_spd, or use GMRES / FGMRES)");
     }
-    int rc = (ws->algo == NK_ALGO_CG) ? cg(ws, A, b, o, st, hist, hist_cap, hist_len)
-                                      : gmres(ws, p, A, b, o, st, hist, hist_cap, hist_len);
+    auto run = [&] {
+        return ws->algo == NK_ALGO_CG       ? cg(ws, A, b, o, st, hist, hist_cap, hist_len)
+               : ws->algo == NK_ALGO_MINRES ? minres(ws, A, b, o, st, hist, hist_cap, hist_len)
+                                            : gmres(ws, p, A, b, o, st, hist, hist_cap, hist_len);
+    };
+    int rc = run();
     if (rc != NK_OK && c->ilu_redo && !ws->u_fused && c->nranks == 1) {
         // a pipelined ILU(0) sweep timed out (reported at the step's sync, not by a sync per apply):
         // the whole solve once more, every ILU(0) apply now on the level sweep (u is still untouched).
@@ -782,8 +938,7 @@ int nk_krylov_solve(nk_workspace* ws, const nk_problem* p, const double* u, cons
         *st = nk_krylov_stats{};
         if (hist_len) *hist_len = 0;
         A.n_matvec = 0;
-        rc = (ws->algo == NK_ALGO_CG) ? cg(ws, A, b, o, st, hist, hist_cap, hist_len)
-                                      : gmres(ws, p, A, b, o, st, hist, hist_cap, hist_len);
+        rc = run();
     }
     c->ilu_redo = false;
     st->n_matvec = A.n_matvec;

@@ -63,7 +63,7 @@ int nk_newton_krylov(nk_ctx* c, const nk_problem* p, double* u, double* res, con
     push(n_res);
     const double tol = o->tol_rel * n_res + o->tol_abs;
     double eta = o->forcing == NK_FORCING_FIXED ? o->eta : o->eta_max;
-    nk_workspace* ws = nullptr;
+    nk_workspace* ws = nullptr;  // (any algo of nk_workspace_create: gmres, fgmres, cg, minres)
     NK_TRY(nk_workspace_create(c, o->algo, p, o->memory > 0 ? o->memory : 20, &ws));
     int rc = NK_OK;
     int64_t outer = 0, inner = 0;

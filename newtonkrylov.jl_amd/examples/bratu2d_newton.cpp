@@ -2,13 +2,15 @@
 // 2D Bratu on an N x N grid, u0 = sin(pi x) sin(pi y), newton_krylov! with GMRES(memory) and the
 // Eisenstat-Walker forcing (src/Ariadne.jl:288-372), FD or exact Jv.  Prints one JSON line.
 //
-//   bin/bratu2d_newton [N=256] [NY] [jv=fd|exact] [memory=30] [restart=1] [--mg] [--mg-semi] [--cg]
+//   bin/bratu2d_newton [N=256] [NY] [jv=fd|exact] [memory=30] [restart=1] [--mg] [--mg-semi] [--cg] [--minres]
 // NY (a number right after N): an N x NY grid on the unit square (h_x != h_y); the JSON line then carries "ny".
 // --mg (anywhere on the line): the geometric multigrid V-cycle as the right preconditioner N (NK_PRECOND_MG).
 // --mg-semi (implies --mg): the hierarchy on the semicoarsened plan (nk_mg_plan_semi / nk_mg_create_levels), for
 // N != NY.  The JSON line then carries "coarsening": "semi".
 // --cg: Newton-CG (examples/bratu.jl:59-63's algo = :cg) instead of GMRES; with --mg the V-cycle in its SPD form
 // (nk_mg_set_spd) is CG's M.  The JSON line then carries "algo": "cg".
+// --minres: Newton-MINRES (NK_ALGO_MINRES) instead of GMRES; with --mg the SPD V-cycle is its M, as for --cg.  The JSON
+// line then carries "algo": "minres".
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -28,12 +30,13 @@
     } while (0)
 
 int main(int argc, char** argv) {
-    bool use_mg = false, use_cg = false, semi = false;
+    bool use_mg = false, use_cg = false, use_minres = false, semi = false;
     int nargs = 1;
-    for (int i = 1; i < argc; ++i) {  // strip --mg / --mg-semi / --cg, keep the positional arguments
+    for (int i = 1; i < argc; ++i) {  // strip --mg / --mg-semi / --cg / --minres, keep the positional arguments
         if (std::strcmp(argv[i], "--mg") == 0) use_mg = true;
         else if (std::strcmp(argv[i], "--mg-semi") == 0) use_mg = semi = true;
         else if (std::strcmp(argv[i], "--cg") == 0) use_cg = true;
+        else if (std::strcmp(argv[i], "--minres") == 0) use_minres = true;
         else argv[nargs++] = argv[i];
     }
     argc = nargs;
@@ -78,8 +81,13 @@ int main(int argc, char** argv) {
     o.memory = memory;
     o.krylov.restart = restart;
     o.krylov.jv_mode = fd ? NK_JV_FD : NK_JV_EXACT;
-    if (use_cg) {
-        o.algo = NK_ALGO_CG;
+    if (use_cg && use_minres) {
+        std::fprintf(stderr, "--cg and --minres exclude each other\n");
+        return 1;
+    }
+    const bool sym = use_cg || use_minres;  // the short recurrences: M (SPD) instead of N
+    if (sym) {
+        o.algo = use_cg ? NK_ALGO_CG : NK_ALGO_MINRES;
         o.krylov.restart = 0;  // a GMRES keyword
     }
     nk_mg* mg = nullptr;
@@ -100,8 +108,8 @@ int main(int argc, char** argv) {
         }
         Nmg.kind = NK_PRECOND_MG;
         Nmg.data = mg;
-        if (use_cg) {
-            CHECK(ctx, nk_mg_set_spd(mg, 1));  // CG's M must be SPD: sigma V, sigma = the sign of J's diagonal
+        if (sym) {
+            CHECK(ctx, nk_mg_set_spd(mg, 1));  // CG's / MINRES's M must be SPD: sigma V, sigma = the sign of J's diagonal
             o.krylov.M = &Nmg;
         } else {
             o.krylov.N = &Nmg;
@@ -122,7 +130,7 @@ int main(int argc, char** argv) {
     std::printf("{\"N\": %lld, %s\"jv\": \"%s\", %s%s%s\"solved\": %s, \"outer\": %lld, \"inner\": %lld, \"n_matvec\": %lld, "
                 "\"n_res\": %.17g, \"tol\": %.17g, \"u_max\": %.17g, \"seconds\": %.6f, \"n_res_history\": [",
                 (long long)N, ny_field, fd ? "fd" : "exact", use_mg ? "\"mg\": true, " : "",
-                semi ? "\"coarsening\": \"semi\", " : "", use_cg ? "\"algo\": \"cg\", " : "",
+                semi ? "\"coarsening\": \"semi\", " : "", use_cg ? "\"algo\": \"cg\", " : (use_minres ? "\"algo\": \"minres\", " : ""),
                 st.solved ? "true" : "false", (long long)st.outer_iterations,
                 (long long)st.inner_iterations, (long long)st.n_matvec, st.n_res, st.tol, umax, secs);
     for (int64_t k = 0; k < nh && k < 64; ++k) std::printf("%s%.17g", k ? ", " : "", hist[k]);

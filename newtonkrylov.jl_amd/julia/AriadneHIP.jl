@@ -20,6 +20,7 @@ const NK_HEAT2D_MIDPOINT, NK_HEAT3D_MIDPOINT, NK_HEAT2D_TRAPEZOID, NK_HEAT3D_TRA
 const NK_BC_ZERO, NK_BC_PERIODIC = Int32(0), Int32(1)
 const NK_USER1D, NK_USER2D, NK_USER3D = Int32(16), Int32(17), Int32(18)
 const NK_JV_EXACT, NK_JV_FD = Int32(0), Int32(1)
+const NK_ALGO_GMRES, NK_ALGO_CG, NK_ALGO_FGMRES, NK_ALGO_MINRES = Int32(0), Int32(1), Int32(2), Int32(3)
 
 check(rc, ctx, what) = rc == 0 || error("$what failed ($rc): " *
                                         unsafe_string(ccall((:nk_last_error, libnkhip), Cstring, (Ptr{Cvoid},), ctx.ptr)))
@@ -557,12 +558,13 @@ function hip_multigrid(J::Ariadne.JacobianOperator; spd = false, coarsening = :f
     empty!(_mg_cache)
     return _mg_cache[key] = HipMultigridPreconditioner(J; spd = spd, coarsening = coarsening, threshold = threshold)
 end
-# the M factory of algo = :cg: newton_krylov!(F!, u, p, res; algo = :cg, M = hip_multigrid_spd)
+# the M factory of algo = :cg and algo = :minres: newton_krylov!(F!, u, p, res; algo = :cg, M = hip_multigrid_spd)
 hip_multigrid_spd(J::Ariadne.JacobianOperator) = hip_multigrid(J; spd = true)
 
 function Krylov.krylov_workspace(method::Symbol, kc::KrylovConstructor{<:HipVector}; memory::Integer = 20)
-    algo = method === :gmres ? Int32(0) : method === :cg ? Int32(1) : method === :fgmres ? Int32(2) :
-           error("HIP path implements :gmres, :fgmres and :cg")
+    # :minres -- the device MINRES for the symmetric stencil Jacobians (M SPD or nothing, no N; `memory` is ignored)
+    algo = method === :gmres ? NK_ALGO_GMRES : method === :cg ? NK_ALGO_CG : method === :fgmres ? NK_ALGO_FGMRES :
+           method === :minres ? NK_ALGO_MINRES : error("HIP path implements :gmres, :fgmres, :cg and :minres")
     res = kc.vm
     r = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:nk_workspace_create, libnkhip), Cint, (VP, Int32, Ref{NkProblem}, Int32, Ref{Ptr{Cvoid}}),
@@ -579,7 +581,7 @@ function Krylov.krylov_solve!(ws::HipKrylovWorkspace, J::HipJacobian, b::HipVect
                               atol::Real = sqrt(eps(Float64)), rtol::Real = sqrt(eps(Float64)),
                               M = nothing, N = nothing, ldiv::Bool = false, kwargs...)
     # Ariadne forwards N = N(J) and M = M(J) when the caller gives them (src/Ariadne.jl:323-329): the
-    # device GMRES / FGMRES applies both (right N, left M); the device CG takes M only
+    # device GMRES / FGMRES applies both (right N, left M); the device CG and MINRES take M only
     isempty(kwargs) || error("AriadneHIP: unsupported Krylov keyword(s) $(join(keys(kwargs), ", "))")
     for P in (N, M)
         P === nothing || P isa HipPreconditioner ||
