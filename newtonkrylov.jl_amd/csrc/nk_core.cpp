@@ -89,6 +89,8 @@ int mb_check(nk_ctx* c) {
         *c->ilu_err = 0;
         c->ilu_pipe_ok = false;  // later sweeps use the one-work-group level sweep
         c->ilu_redo = true;      // nk_krylov_solve / nk_precond_apply redo their work once on it
+        // the notice ilu_pipe_failed gives: the context has left its fast path for good
+        std::fprintf(stderr, "[nkhip] pipelined ILU(0) sweep timed out; the level sweep is used from now on\n");
         return fail(c, NK_E_HIP, "pipelined ILU(0) sweep: a strip's progress never arrived (timeout); pipelined sweep disabled");
     }
     return NK_OK;
