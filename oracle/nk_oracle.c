@@ -1206,6 +1206,18 @@ void oc_exp(int64_t n, const double* x, double* y) {
 void oc_exp_slow(int64_t n, const double* x, double* y) {
     for (int64_t i = 0; i < n; ++i) y[i] = nkx_exp_slow(x[i]);
 }
+/* mask[i] = 1 where the fast phase does not settle x[i] (nkx_exp_fast returns 0): the inputs the device's
+ * exp hands to its exact phase -- the same source, so the same decision */
+void oc_exp_rare(int64_t n, const double* x, int32_t* mask) {
+    for (int64_t i = 0; i < n; ++i) {
+        double y;
+        mask[i] = !nkx_exp_fast(x[i], &NKX_T[0][0], &y);
+    }
+}
+/* the fast phase's value alone (what nkx_exp_fast stores, whether or not its rounding test settles x) */
+void oc_exp_fast(int64_t n, const double* x, double* y) {
+    for (int64_t i = 0; i < n; ++i) (void)nkx_exp_fast(x[i], &NKX_T[0][0], &y[i]);
+}
 /* the fast phase alone: exp(x) ~ (zh + zl) 2^m; returns how many inputs the Ziv test sent to the slow phase */
 int64_t oc_exp_dd(int64_t n, const double* x, double* zh, double* zl, int32_t* m) {
     int64_t slow = 0;

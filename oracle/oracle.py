@@ -139,6 +139,8 @@ def lib():
         L.oc_exp_slow.argtypes = [I64, P, P]
         L.oc_exp_dd.argtypes = [I64, P, P, P, C.POINTER(C.c_int32)]
         L.oc_exp_dd.restype = I64
+        L.oc_exp_rare.argtypes = [I64, P, C.POINTER(C.c_int32)]
+        L.oc_exp_fast.argtypes = [I64, P, P]
         _lib = L
     return _lib
 
@@ -507,6 +509,24 @@ def exp_slow(x) -> np.ndarray:
     x = np.ascontiguousarray(x, dtype=np.float64)
     y = np.empty_like(x)
     lib().oc_exp_slow(x.size, _p(x), _p(y))
+    return y
+
+
+def exp_rare(x) -> np.ndarray:
+    """Where nk_exp's fast phase does not settle x (nkx_exp_fast returns 0) and the exact phase runs: a bool
+    array of x's shape -- the decision the device makes, from the source it compiles."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    mask = np.empty(x.shape, dtype=np.int32)
+    lib().oc_exp_rare(x.size, _p(x), mask.ctypes.data_as(C.POINTER(C.c_int32)))
+    return mask != 0
+
+
+def exp_fast(x) -> np.ndarray:
+    """The value nk_exp's fast phase leaves (on x clamped into its range), settled or not: what a kernel
+    that skipped the exact phase would return."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.empty_like(x)
+    lib().oc_exp_fast(x.size, _p(x), _p(y))
     return y
 
 

@@ -108,6 +108,36 @@ def test_ziv_cases_take_the_exact_phase():
     assert np.all(oc.exp(x) == _mp_exp(x))
 
 
+def test_ziv_fixture_takes_the_exact_phase(golden_dir):
+    """tests/golden/exp_ziv.npz (make_exp_ziv.py): generic inputs of the Bratu range that the fast phase does
+    not settle, which tests/test_hip_exp_rare.py plants in the Bratu grids.  Every one still takes the exact
+    phase -- a change of nk_exp.h that lets the fast phase settle them fails here instead of silently
+    emptying those tests -- and the result is mpmath's correctly rounded value."""
+    d = np.load(os.path.join(golden_dir, "exp_ziv.npz"))
+    x, y = d["x"], d["y"]
+    assert len(x) >= 48 and len(np.unique(x)) == len(x) and np.all((x > -1.0) & (x < 3.0))
+    assert oc.exp_rare(x).all()
+    assert np.array_equal(oc.exp(x), y)
+    assert np.array_equal(y, _mp_exp(x))
+
+
+def test_exp_rare_mask_is_the_fast_phase_decision():
+    """oc.exp_rare is elementwise nkx_exp_fast's verdict: its count is oc.exp_dd's, the whole positive Ziv
+    family and every out-of-range / non-finite input are rare, ordinary inputs almost never."""
+    a = np.arange(2 ** 16, 2 ** 16 + 3000, dtype=np.float64)
+    fam = a * 2.0 ** -52 + 2.0 ** -53
+    assert oc.exp_rare(fam).all()
+    assert oc.exp_rare(np.array([710.0, -720.0, -745.0, -746.0, np.nan, np.inf, -np.inf])).all()
+    x = np.random.default_rng(10).uniform(-1.0, 3.0, 1_000_000)
+    m = oc.exp_rare(x.reshape(1000, 1000))
+    assert m.shape == (1000, 1000) and m.dtype == bool
+    assert m.sum() == oc.exp_dd(x)[3] <= 40
+    assert not oc.exp_rare(np.array([0.0, 1.0, 2.0, -1.0])).any()
+    # the fast phase's own value: the correctly rounded one wherever it settles, and on the family too
+    assert np.array_equal(oc.exp_fast(x)[~m.ravel()], oc.exp(x)[~m.ravel()])
+    assert np.array_equal(oc.exp_fast(fam), oc.exp(fam))
+
+
 def test_fast_phase_error_bound():
     """The fast phase's double-double result is within 2^-76 (relative) of exp(x) -- the bound DESIGN.md
     §2 derives; the Ziv test is valid up to 2^-73 (measured ~2^-79).  Random inputs over the Bratu and the
