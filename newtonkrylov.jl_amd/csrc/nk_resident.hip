@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <type_traits>
 #include <vector>
 
 #include "nk_device.hpp"
@@ -30,6 +31,16 @@ namespace {
 // Requires all G blocks co-resident: G = #CUs, 1 block per CU (the LDS share forces it).
 constexpr int kResMax = 64;  // passes per launch (reorthogonalisation: 2k)
 constexpr int kResThreads = 256;
+// tail-group size of a fully resident sweep (LDS slots; 0 = off): -DNK_RES_TAIL_DEFAULT=g for a `make variant`
+// A/B of the product build; the kbench build reads NK_RES_TAIL instead.
+#ifndef NK_RES_TAIL_DEFAULT
+#define NK_RES_TAIL_DEFAULT 24
+#endif
+constexpr int kResTail = NK_RES_TAIL_DEFAULT;
+#ifdef NK_KBENCH
+int g_res_tail_hook = -1;     // nkb_mgs_res_tail: the tail size of its launches (overrides NK_RES_TAIL), -1 = none
+int g_res_tail_launched = 0;  // A.tg of the last launch
+#endif
 struct ResArgs {
     const double* V[kResMax + 1];  // pass t: V_i = V[t], V_{i+1} = V[t + 1]
     double* q;
@@ -55,6 +66,7 @@ struct ResArgs {
     int jv_on;
     int64_t n2;            // double2 elements
     int np, red_len, rl;
+    int tg;                // tail group: the last tg of the rl LDS slots are updated first and dotted last in every pass
     unsigned tag0, mb0, spin;
 };
 
@@ -294,6 +306,56 @@ __device__ __forceinline__ double res_pass(const ResArgs& A, ResState<RV>& S, dx
     const dx2* vl = vb + RV * ss;
     const dx2* wl = wb + RV * ss;
     const int rl = A.rl;
+    // tail group (full residency only; never on a reversed pass): the last tg LDS slots leave the fused
+    // loop.  Their update, elementwise and so free of any order, runs first, on the V_i lines this CU
+    // loaded last in the previous pass as its V_{i+1} (nothing but the prefetch was loaded since: still
+    // in this XCD's L2); their dot runs last, in slot order, so the chain of partial sums is unchanged
+    const int tg = rev ? 0 : A.tg;
+    const int rf = rl - tg;  // LDS slots of the fused loop
+    auto tail_upd = [&](int s, auto nb) {  // slots s .. s+N-1: q -= h V_i, default load policy
+        constexpr int N = decltype(nb)::value;
+        dx2 bv[N];
+#pragma unroll
+        for (int u = 0; u < N; ++u) bv[u] = vl[(s + u) * ss];
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+            dx2 a = lq[(s + u) * kResThreads + tid];
+            a.x = fma(mh, bv[u].x, a.x);
+            a.y = fma(mh, bv[u].y, a.y);
+            lq[(s + u) * kResThreads + tid] = a;
+        }
+    };
+    auto tail_dot = [&](int s, auto nb) {  // slots s .. s+N-1: the partial of <V_{i+1}, q> or <q, q>
+        constexpr int N = decltype(nb)::value;
+        if (next) {
+            dx2 cv[N];
+#pragma unroll
+            for (int u = 0; u < N; ++u) cv[u] = wl[(s + u) * ss];
+#pragma unroll
+            for (int u = 0; u < N; ++u) {
+                const dx2 a = lq[(s + u) * kResThreads + tid];
+                acc = fma(cv[u].x, a.x, acc);
+                acc = fma(cv[u].y, a.y, acc);
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < N; ++u) {
+                const dx2 a = lq[(s + u) * kResThreads + tid];
+                acc = fma(a.x, a.x, acc);
+                acc = fma(a.y, a.y, acc);
+            }
+        }
+    };
+    auto tail = [&](auto&& f) {  // batches of 8 slots (8 16-B loads in flight per lane, as a fused batch of 4), then singles
+        int s = rf;
+        __builtin_amdgcn_sched_barrier(0);  // no fused-phase load hoisted into a tail batch: registers hold q
+        for (; s + 8 <= rl; s += 8) {
+            f(s, std::integral_constant<int, 8>{});
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        for (; s < rl; ++s) f(s, std::integral_constant<int, 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+    };
     auto lds = [&] {
         auto one4 = [&](int s, bool down) {  // LDS slots s .. s+3 (down: s+3 .. s)
             dx2 bv[4], cv[4];
@@ -331,20 +393,20 @@ __device__ __forceinline__ double res_pass(const ResArgs& A, ResState<RV>& S, dx
                 lq[(s + u) * kResThreads + tid] = a;
             }
         };
-        const int r4 = rl / 4 * 4;
+        const int r4 = rf / 4 * 4;
         if (!rev && LB != 4) {
-            const int rb = rl / LB * LB;
+            const int rb = rf / LB * LB;
             for (int s = 0; s < rb; s += LB) oneB(s);
             for (int s = rb; s < r4; s += 4) one4(s, false);
-            for (int s = r4; s < rl; ++s) one(s);
+            for (int s = r4; s < rf; ++s) one(s);
         } else if (!rev) {
             for (int s = 0; s < r4; s += 4) one4(s, false);
-            for (int s = r4; s < rl; ++s) one(s);
+            for (int s = r4; s < rf; ++s) one(s);
         } else if (PRE && B == 4 && RV >= B) {
             // ALT with PRE: groups of 4 from the top (the first one preloaded across the hand-off,
-            // the previous pass's last V_{i+1} lines), then the rl % 4 lowest slots
+            // the previous pass's last V_{i+1} lines), then the rf % 4 lowest slots
             {
-                const int s = rl - 4;
+                const int s = rf - 4;
 #pragma unroll
                 for (int u0 = 0; u0 < 4; ++u0) {
                     const int u = 3 - u0;
@@ -353,11 +415,11 @@ __device__ __forceinline__ double res_pass(const ResArgs& A, ResState<RV>& S, dx
                     lq[(s + u) * kResThreads + tid] = a;
                 }
             }
-            int s = rl - 8;
+            int s = rf - 8;
             for (; s >= 0; s -= 4) one4(s, true);
             for (s += 3; s >= 0; --s) one(s);
         } else {
-            for (int s = rl - 1; s >= r4; --s) one(s);
+            for (int s = rf - 1; s >= r4; --s) one(s);
             for (int s = r4 - 4; s >= 0; s -= 4) one4(s, true);
         }
     };
@@ -407,8 +469,10 @@ __device__ __forceinline__ double res_pass(const ResArgs& A, ResState<RV>& S, dx
         }
     };
     if (rev) lds();
+    tail(tail_upd);
     regs();
     if (!rev) lds();
+    tail(tail_dot);
     stream();
     return acc;
 }
@@ -657,6 +721,18 @@ int launch_mgs_sweep(nk_ctx* c, int64_t n, double* q, const double* const* V, in
         static const int strided_env = NK_TUNE("NK_RES_STRIDED", 0);
         A.strided = strided_env && n2 % kResThreads == 0 && ns % G == 0 && ns / G == rv + A.rl;
         A.mirror = NK_TUNE("NK_RES_MIRROR", 0) && !A.strided && n2 % kResThreads == 0 && ns % G == 0 && ns / G == rv + A.rl;
+        // tail group: only where all of q is resident -- the streamed remainder follows the
+        // LDS slots in the chain of partial sums and loads between the tail's two phases -- and never
+        // with the alternating slot orders (kbench variants 2 and 11), which end a pass elsewhere
+        static const int tail_env = NK_TUNE("NK_RES_TAIL", kResTail);
+        int tail = tail_env;
+#ifdef NK_KBENCH
+        if (g_res_tail_hook >= 0) tail = g_res_tail_hook;
+#endif
+        A.tg = full && xv != 2 && xv != 11 ? std::max(0, std::min(tail, A.rl)) : 0;
+#ifdef NK_KBENCH
+        g_res_tail_launched = A.tg;
+#endif
     }
 #ifdef NK_KBENCH
     if (jin) {
@@ -788,7 +864,11 @@ __global__ __launch_bounds__(kBlock) void k_hashfill(int64_t n, double* __restri
 // (launch_mgs_pass) on the same q and basis: us_out / us_ref = microseconds per pass of each;
 // diff_out = max |q_res - q_chain| / max |q_chain| after the sweep, and the largest relative
 // difference of the Hessenberg column in diff_out[1].
-extern "C" int nkb_mgs_res(nk_ctx* c, int64_t n, int k, int rv, int reps, double* us_out, double* us_ref, double* diff_out) {
+// tail >= 0: the sweep's tail-group size instead of NK_RES_TAIL (the host rule still clamps it and
+// turns it off without full residency); tail_out: the size the sweep launched with; q_out (n) and
+// col_out (k + 1): the sweep's q and Hessenberg column, to compare two schedules bit for bit.
+static int mgs_res_bench(nk_ctx* c, int64_t n, int k, int rv, int tail, int reps, double* us_out, double* us_ref,
+                         double* diff_out, double* q_out, double* col_out, int* tail_out) {
     using namespace nk;
     if (!c || n < 2 || k < 1 || k > kResMax || reps < 1 || !us_out || !us_ref || !diff_out) return NK_E_ARG;
     // NK_RES_TSTAMP=<file>: also dump the per-pass, per-block wall clocks of the last timed sweep
@@ -832,7 +912,9 @@ extern "C" int nkb_mgs_res(nk_ctx* c, int64_t n, int k, int rv, int reps, double
         NK_TRY(launch_copy(c, n, qb, q0));
         NK_TRY(launch_dot(c, n, V[0], qb, &red));
         NK_HIP(c, hipEventRecord(e0, c->stream));
+        g_res_tail_hook = tail;
         const int rc = launch_mgs_sweep(c, n, qb, V.data(), k, k, red, col2, nullptr, rv, nullptr, nullptr);
+        g_res_tail_hook = -1;
         if (rc != NK_OK) return rc == 1 ? fail(c, NK_E_ARG, "resident sweep not applicable") : rc;
         NK_HIP(c, hipEventRecord(e1, c->stream));
         NK_HIP(c, hipEventSynchronize(e1));
@@ -856,6 +938,9 @@ extern "C" int nkb_mgs_res(nk_ctx* c, int64_t n, int k, int rv, int reps, double
     diff_out[0] = m > 0 ? d / m : d;
     diff_out[1] = dh;
     diff_out[2] = (double)c->res_rl;
+    if (tail_out) *tail_out = g_res_tail_launched;
+    if (q_out) std::copy(b.begin(), b.end(), q_out);
+    if (col_out) std::copy(cb.begin(), cb.end(), col_out);
     if (c->res_tstamp && tsf && *tsf) {
         std::vector<uint64_t> ts((size_t)2 * k * c->res_blocks);
         NK_HIP(c, hipMemcpy(ts.data(), c->res_tstamp, sizeof(uint64_t) * ts.size(), hipMemcpyDeviceToHost));
@@ -872,4 +957,17 @@ extern "C" int nkb_mgs_res(nk_ctx* c, int64_t n, int k, int rv, int reps, double
     for (auto p : Vbase) (void)hipFree(p);
     return NK_OK;
 }
+
+extern "C" int nkb_mgs_res(nk_ctx* c, int64_t n, int k, int rv, int reps, double* us_out, double* us_ref, double* diff_out) {
+    return mgs_res_bench(c, n, k, rv, -1, reps, us_out, us_ref, diff_out, nullptr, nullptr, nullptr);
+}
+
+extern "C" int nkb_mgs_res_tail(nk_ctx* c, int64_t n, int k, int rv, int tail, int reps, double* us_out, double* us_ref,
+                                double* diff_out, double* q_out, double* col_out, int* tail_out) {
+    if (!tail_out) return NK_E_ARG;
+    return mgs_res_bench(c, n, k, rv, tail, reps, us_out, us_ref, diff_out, q_out, col_out, tail_out);
+}
+
+// the tail-group size of this process's last resident sweep launch (a solve's as well as the hook's)
+extern "C" int nkb_res_tail_last(void) { return nk::g_res_tail_launched; }
 #endif  // NK_KBENCH

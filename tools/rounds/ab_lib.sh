@@ -4,7 +4,7 @@
 # --workload arguments ('|'-separated), ROUNDS alternating rounds.  One line per run: matvecs/s and the
 # kernels above 1 % of the time (average microseconds per launch).
 set -e
-cd "$(dirname "$0")/.."
+cd "$(dirname "$0")/../.."
 B="timeout -k 10 240 python -u bench.py --no-cpu-baseline"
 IFS='|' read -ra VS <<< "${LIBS:?}"
 IFS='|' read -ra WLS <<< "${WL:-bratu2d}"
