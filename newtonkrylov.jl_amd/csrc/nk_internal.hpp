@@ -14,22 +14,18 @@
 #include <vector>
 
 #include "nkhip.h"
+#include "nk_plan.hpp"
 
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 namespace nk {
 
-constexpr int kBlock = 256;          // threads per block for every streaming kernel (4 waves of 64)
-constexpr int kMaxRedBlocks = 2048;  // partial sums per reduction (8 blocks per CU on 256 CUs)
+// (kBlock, kMaxRedBlocks, kRedCap, kTileCap, kTileParts, Mode: nk_plan.hpp)
 constexpr int kRedSlots = 4;         // ring of partial-sum slots
-constexpr int kRedCap = 16384;       // doubles per slot (a stencil launch may have more blocks)
-constexpr int kTileCap = 1 << 19;    // one-shot stencil tiles per launch (per-tile partials before the group fold)
-constexpr int kTileParts = 1024;     // partials a one-shot stencil launch hands on (tiles folded in groups)
 constexpr int kScalCap = 8192;       // device scalar area (Hessenberg column, y, norms)
 constexpr int kMaxUpdateVecs = 32;   // basis vectors folded per x-update launch
 constexpr int kMgsVariant = 5;       // MGS-pass variant (unroll x non-temporal V_i), see mgs_dispatch
 
-enum Mode { MODE_RES = 0, MODE_JEXACT = 1, MODE_JFD = 2 };
 enum Epi {
     EPI_NONE = 0, EPI_SUMSQ = 1, EPI_DOT = 2, EPI_RESID = 3,
     EPI_DOTV = 4,   // kernel-internal: EPI_DOT + vout (V_k = v / h stored)

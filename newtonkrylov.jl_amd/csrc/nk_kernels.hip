@@ -453,28 +453,16 @@ double* red_out(nk_ctx* c, int len, Red* r, int* fin) {
     return part;
 }
 
+// the streaming grids (nk_plan.hpp) under this build's caps
 int red_blocks(int64_t n) {
     static const int cap = NK_TUNE("NK_RED_BLOCKS", kMaxRedBlocks);
-    int64_t g = (n + 2LL * kBlock * 4 - 1) / (2LL * kBlock * 4);  // >= 4 double2 per thread
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
+    return red_blocks(n, cap);
 }
 
-// Grid of the streaming kernels whose partials (if any) only a one-block finaliser reads: up to
-// kRedCap - 2 blocks, >= 2 double2 per thread.  Many short-lived blocks stream faster than a
-// grid of 8 per CU looping over block chunks (tools/stream_probe.py: a plain copy 5.0 -> 6.2 TB/s;
-// k_update_x -9 % on heat 8192^2, profiles/r02/ab_redblocks.log).  Reductions consumed by every
-// block of the next kernel (dot, sumsq, the MGS chain) keep red_blocks: each consumer block sums
-// all the partials.
 int wide_blocks(int64_t n) {
     static const int cap = std::max(1, std::min(kRedCap - 2, NK_TUNE("NK_WIDE_BLOCKS", kRedCap - 2)));
-    int64_t g = (n + 2LL * kBlock * 2 - 1) / (2LL * kBlock * 2);
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
+    return wide_blocks(n, cap);
 }
-
 
 
 namespace {
@@ -554,6 +542,86 @@ int blk_order(nk_ctx* c, const KArgs& A, int nzc, const int** out) {
     *out = c->blk_order;
     return NK_OK;
 }
+// the tile rule's knobs (st_plan, nk_plan.hpp), read once per process
+const StKnobs& st_knobs() {
+    static const StKnobs once = [] {
+        const StKnobs D;
+        StKnobs K;
+        K.vec_pref = NK_TUNE("NK_ST_VEC", D.vec_pref);
+        K.blocks = NK_TUNE("NK_ST_BLOCKS", D.blocks);
+        K.min_rows = NK_TUNE("NK_ST_MINROWS", D.min_rows);
+        K.max_rows = NK_TUNE("NK_ST_MAXROWS", D.max_rows);
+        K.oneshot = NK_TUNE("NK_ST_ONESHOT", D.oneshot);
+        K.lds3 = NK_TUNE("NK_ST3_LDS", D.lds3);
+        K.nw3 = NK_TUNE("NK_ST3_NW", D.nw3);
+        K.blocks3 = NK_TUNE("NK_ST3_BLOCKS", D.blocks3);
+        K.min_planes = NK_TUNE("NK_ST_MINPLANES", D.min_planes);
+        K.zalt = NK_TUNE("NK_ST3_ZALT", D.zalt);
+        K.ymarch = NK_TUNE("NK_ST3_YMARCH", D.ymarch);
+        K.ym_rows = NK_TUNE("NK_ST3Y_ROWS", D.ym_rows);
+        K.f0r = NK_TUNE("NK_F0R", D.f0r);
+        K.tile_parts = std::max(1, std::min(kRedCap - 2, NK_TUNE("NK_TILE_PARTS", D.tile_parts)));
+        return K;
+    }();
+    return once;
+}
+
+// how the ghost layers of a launch's v arrive
+enum Halo { HALO_NONE, HALO_SEPARATE, HALO_SLAB, HALO_BLOCK };  // fresh; exchanged first; in the launch: slab planes, block faces
+
+Halo halo_form(nk_ctx* c, const StencilIn& in, const Geo& g, const StPlan& P, bool blk, int rows_override) {
+    if (!in.xchg_v) return HALO_NONE;
+    const nk_problem* p = in.p;
+    const int fuse_env = halo_fuse_knob();
+    // ranks sharing one GPU (rehearsals): in-launch only for small slabs -- a big slab's end tiles spin
+    // on CUs the peer's producing tiles need (r05: 8 ranks x 256^2 x 32 planes, 30.5 s per step fused;
+    // 26.7 ms with the exchange kernel, profiles/r06/rehearsal8_heat3d_256_slabs.json, the default
+    // spin limit).  Neighbours must agree on the form (tile flags vs
+    // the exchange kernel's block flags), so the test uses rank-uniform values only: the most ranks on
+    // one GPU and the slab size estimated from the global spacing, never this rank's slab
+    static const int64_t fuse_max = env_cfg("NK_SHARED_FUSE_MAX", 0) > 0 ? env_cfg("NK_SHARED_FUSE_MAX", 0) : kSharedFuseMax;
+    if (blk) {  // 3D blocks: k_faces_ipc first, or (opt-in) every ghost layer inside this launch
+        // In-launch (blk_tile_exchange) is bitwise the same but SLOWER on one GPU, the only place it can be
+        // measured here: the self-block 256^3 Jv 145 + 22 us (faces kernel) -> 187 us in-launch (2x2x2, every
+        // tile exchanges x patches and waits a round trip), 145 + 21 -> 172 us at 1x2x4 (profiles/r06/
+        // ab_blk_*.json).  NK_BLK_INLAUNCH=1 keeps it reachable for xGMI, where the separate kernel's
+        // transfer -- not a round trip -- would dominate (unmeasured)
+        static const int blk_in_env = env_cfg("NK_BLK_INLAUNCH", 0);
+        const bool bfuse = blk_in_env && fuse_env && c->mb_on && in.mode != MODE_RES && rows_override <= 0 &&
+                           blk_inlaunch_ok(c, p, fuse_max);
+        return bfuse ? HALO_BLOCK : HALO_SEPARATE;
+    }
+    // slabs: through the peers' inboxes inside this launch (halo_tile_exchange: only the tiles at the
+    // slab's ends fetch, the rest of the grid never waits) when the peer mailbox is up, the slab axis is
+    // not periodic and every tile of a plane has a flag; else exchanged first
+    const int64_t tiles_pl = g.dim == 2 ? P.tiles_x : (int64_t)P.tiles_x * P.tiles_y;
+    const bool share_ok = c->share_most <= 1 || shared_slab_points(c, p, g) <= fuse_max;
+    const bool fuse = fuse_env && c->mb_on && (c->nranks > 1 || halo_self_ring(c)) && share_ok && p->bc != NK_BC_PERIODIC &&
+                      in.mode != MODE_RES && (g.dim == 2 || (g.dim == 3 && P.lds3)) && g.plane <= c->halo_cap &&
+                      tiles_pl <= kHaloTileFlags;
+    return fuse ? HALO_SLAB : HALO_SEPARATE;
+}
+
+// algorithmic (compulsory) bytes per launch, for the instantiation the dispatch launched (StInst: an
+// F0R kernel reads no F0)
+double st_bytes(const StencilIn& in, int64_t n, const StInst& st) {
+    const bool heat = nk_is_heat(in.p->kind);
+    int words = 1;  // out
+    if (in.mode == MODE_RES) words += 1 + (heat ? 1 : 0);
+    else if (in.mode == MODE_JEXACT) words += 1 + (heat ? 0 : 1);
+    else words += 3 + (heat ? 1 : 0) - (st.f0r ? 1 : 0);
+    if (in.epi == EPI_RESID || (in.epi == EPI_DOT && in.aux)) words += 1;
+    if (in.vout) words += 1;  // fused kdivcopy!: V_k is written
+    return 8.0 * words * (double)n;
+}
+
+// profile classes by mode and epilogue; normalise-and-store V_k and its V_1 = r0 / beta form, whose dot
+// partner is the stored vector itself, are distinct instantiations with profile lines of their own
+const char* const kStNames[3][4] = {{"residual", "residual_norm", "residual_dot", "residual_resid"},
+                                    {"jv_exact", "jv_exact_sumsq", "jv_exact_dot", "jv_exact_resid"},
+                                    {"jv_fd", "jv_fd_sumsq", "jv_fd_dot", "jv_fd_resid"}};
+const char* const kStFusedNames[3] = {"residual", "jv_exact_dot_norm", "jv_fd_dot_norm"};
+const char* const kStV1Names[3] = {"residual", "jv_exact_dot_v1", "jv_fd_dot_v1"};
 }  // namespace
 
 int launch_stencil(nk_ctx* c, const StencilIn& in, Red* red) {
@@ -564,11 +632,15 @@ int launch_stencil(nk_ctx* c, const StencilIn& in, Red* red) {
     return launch_stencil_ex(c, in, red, 0, 0);
 }
 
-
 int launch_stencil_ex(nk_ctx* c, const StencilIn& in, Red* red, int rows_override, int fast) {
     const nk_problem* p = in.p;
     Geo g;
     NK_TRY(geometry(c, p, &g));
+    const bool per = p->bc == NK_BC_PERIODIC, blk = blocks3d(c, g);
+    const bool vstore = in.vout && in.epi == EPI_DOT;
+    const StPlan P = st_plan(StShape{g.dim, p->nx, p->ny, p->nz, per, blk, in.mode, nk_is_heat(p->kind), nk_scheme(p->kind),
+                                     vstore, in.aux != nullptr, rows_override, fast, in.f0r},
+                             st_knobs());
     KArgs A{};
     A.out = in.out; A.u = in.u; A.v = in.v; A.F0 = in.F0; A.un = p->un; A.aux = in.aux;
     A.nx = p->nx; A.ny = p->ny; A.nz = p->nz;
@@ -582,222 +654,58 @@ int launch_stencil_ex(nk_ctx* c, const StencilIn& in, Red* red, int rows_overrid
     A.vout = in.vout;
     A.ihx2 = 1.0 / A.hx2; A.ihy2 = 1.0 / A.hy2; A.ihz2 = 1.0 / A.hz2; A.ieps = in.eps != 0.0 ? 1.0 / in.eps : 0.0;
     A.alpha = p->alpha;
-    const bool per = p->bc == NK_BC_PERIODIC;
-    int vec = 1, grid = 1;
-    if (g.dim == 1) {
-        grid = (int)((p->nx + kBlock - 1) / kBlock);
-    } else if (g.dim == 2) {
-        static const int vec_pref = NK_TUNE("NK_ST_VEC", 2);
-        vec = (p->nx % 2 == 0) ? 2 : 1;
-        if (((fast & 4) || vec_pref == 4) && p->nx % 4 == 0 && !per) vec = 4;
-        A.tiles_x = (int)((p->nx + kBlock * vec - 1) / (kBlock * vec));
-        // rows per tile: about 1024 tiles, between 8 and 32 rows (4096^2: 32-row tiles, FD Jv 121.3 ->
-        // 114.8 us and +0.6 % on the bench, profiles/r02/ab_st_blocks.log; 8192^2 heat: 32 rows are
-        // as fast as 64 for the FD Jv and 3 % faster for the residual, kbench_st2d_8192.log), and
-        // never more tiles than the reduction slot holds partials
-        static const int target = NK_TUNE("NK_ST_BLOCKS", 1024);
-        int64_t rows = (p->ny * A.tiles_x + target - 1) / target;
-        static const int min_rows = NK_TUNE("NK_ST_MINROWS", 8);
-        static const int max_rows = NK_TUNE("NK_ST_MAXROWS", 32);
-        if (rows > max_rows) rows = max_rows;
-        if (rows < min_rows) rows = min_rows;
-        const int64_t cap_rows = (p->ny * A.tiles_x + (kRedCap - 3)) / (kRedCap - 2);
-        if (rows < cap_rows) rows = cap_rows;
-        if (rows_override > 0) rows = rows_override;
-        if (rows > p->ny) rows = p->ny;
-        A.rows = (int)rows;
-        A.tiles_y = (int)((p->ny + rows - 1) / rows);
-        grid = A.tiles_x * A.tiles_y;
-        A.lin = (fast & 2048) ? 1 : 0;  // kbench: tiles in address order
-        // kbench only: one-shot LDS tiles (k_st2t: 8 rows x 128 columns, no march, tiles in address
-        // order, block partials folded by k_tile_fold) for the FD operator (NK_ST_ONESHOT=1), or for any
-        // mode with fast bits 8192 / 16384 / 32768 (8 / 4 / 16 rows); 262144 forces the march.  8-12 %
-        // faster than the march in isolation (profiles/r03/ab_tile8.log, ab_oneshot_fold2.log), but not in
-        // the bench (ab_oneshot4.log): the product keeps the march.
-        static const int oneshot_env = NK_TUNE("NK_ST_ONESHOT", 0);
-        A.tile2 = (fast & 8192) ? 8 : ((fast & 16384) ? 4 : ((fast & 32768) ? 16 : 0));
-        if (!A.tile2 && oneshot_env && in.mode == MODE_JFD && vec == 2 && !(fast & (262144 | 4 | 2048)) &&
-            rows_override <= 0 && !(oneshot_env == 2 && nk_scheme(p->kind) == 2))
-            A.tile2 = 8;
-        // fast bit 131072 with a one-shot tile: 256 columns wide (VEC 4), 8 or 4 rows
-        if (A.tile2 && (fast & 131072) && p->nx % 4 == 0 && !per && !(A.tile2 == 16)) {
-            vec = 4;
-            A.tiles_x = (int)((p->nx + 255) / 256);
-            A.tiles_y = (int)((p->ny + A.tile2 - 1) / A.tile2);
-            grid = A.tiles_x * A.tiles_y;
-        } else if (A.tile2 && vec == 2) {
-            const int tx1 = (int)((p->nx + 127) / 128), ty1 = (int)((p->ny + A.tile2 - 1) / A.tile2);
-            if ((int64_t)tx1 * ty1 <= kTileCap) {
-                A.tiles_x = tx1;
-                A.tiles_y = ty1;
-                grid = A.tiles_x * A.tiles_y;
-            } else {
-                A.tile2 = 0;  // beyond the per-tile partial buffer: the row march
-            }
-        } else {
-            A.tile2 = 0;
-        }
-    } else {
-        vec = (p->nx % 2 == 0) ? 2 : 1;
-        if (blocks3d(c, g)) {  // 3D blocks: x / y ghost layers from the faces after the trailing plane
-            A.blk = 1;
-            A.fy = g.n + g.plane;
-            A.fx = A.fy + 2 * p->nx * p->nz;
-            for (int sd = 2; sd < kHaloSides; ++sd)
-                if (block_nbr(c, sd) >= 0) A.nbm |= 1 << sd;
-        }
-        // rows per 3D tile and the y-neighbour path (k_st3d loads, k_st3l LDS); fast bits 8 / 16 select
-        // k_st3l with 4 / 8 rows (kernel-variant bench), NK_ST3_LDS / NK_ST3_NW likewise
-        // k_st3l with 4-row tiles is the default: +6-16 % over k_st3d on every 3D kind / mode at 512^3
-        // and at config 5's 512^2 x 64 slab (profiles/r02/kbench_st3l.log)
-        static const int lds_env = NK_TUNE("NK_ST3_LDS", 1);
-        static const int nw_env = NK_TUNE("NK_ST3_NW", 4);
-        A.lds3 = (fast & 24) ? 1 : lds_env;
-        A.nw = A.lds3 ? ((fast & 8) ? 4 : ((fast & 16) ? 8 : (nw_env == 4 ? 4 : 8))) : 4;
-        if (A.blk) {  // 3D blocks: k_st3l with 4-row tiles (the kernel-variant build's other forms have no faces)
-            A.lds3 = 1;
-            A.nw = 4;
-        }
-        A.tiles_x = (int)((p->nx + 64 * vec - 1) / (64 * vec));
-        A.tiles_y = (int)((p->ny + A.nw - 1) / A.nw);
-        static const int target = NK_TUNE("NK_ST3_BLOCKS", 8192);  // shorter z-marches keep y-adjacent tiles in step (L2 reuse of the halo rows)
-        int64_t planes = ((int64_t)p->nz * A.tiles_x * A.tiles_y + target - 1) / target;
-        static const int min_planes = NK_TUNE("NK_ST_MINPLANES", 16);  // 16: (16 + 2) / 16 z-halo re-reads
-        if (planes < min_planes || A.blk) planes = min_planes;  // (blocks: one chunk size on every rank -- the
-                                                                 //  in-launch exchange numbers x / y patches by chunk)
-        if (rows_override > 0) planes = rows_override;
-        if (planes > p->nz) planes = p->nz;
-        A.rows = (int)planes;
-        grid = A.tiles_x * A.tiles_y * (int)((p->nz + planes - 1) / planes);
-        // k_st3l tile order / march direction (tile3_of; kbench only: 1 whole tile columns per XCD band with
-        // odd z-chunks marching down, 2 plane-major + odd chunks down, 3 chunk pairs): within +-3 % of the
-        // plane-major order, upward marches (0, the product) -- profiles/r03/ab_zalt*.log
-        static const int zalt_env = NK_TUNE("NK_ST3_ZALT", 0);
-        A.zalt = (A.lds3 && !(fast & 65536) && !A.blk) ? zalt_env : 0;  // kbench fast bit 65536: the plane-major order
-        // the y-march (k_st3y, kbench NK_ST3_YMARCH=1: slabs short along z; NK_ST3Y_ROWS rows per chunk):
-        // tiles of nw planes x 64 vec columns marching a chunk of rows
-        static const int ym_env = NK_TUNE("NK_ST3_YMARCH", 0);
-        static const int ym_rows = NK_TUNE("NK_ST3Y_ROWS", 64);
-        A.ym = (A.lds3 && (ym_env || (fast & 524288)) && rows_override <= 0 && !A.zalt && !A.blk) ? 1 : 0;  // (bit 2^19: the y-march)
-        if (A.ym) {
-            const int64_t r = std::min<int64_t>(std::max(1, ym_rows), p->ny);
-            A.rows = (int)r;
-            A.tiles_y = (int)((p->ny + r - 1) / r);
-            grid = A.tiles_x * A.tiles_y * (int)((p->nz + A.nw - 1) / A.nw);
-        }
+    A.tiles_x = P.tiles_x; A.tiles_y = P.tiles_y; A.rows = P.rows;
+    A.lin = P.lin; A.tile2 = P.tile2;
+    A.lds3 = P.lds3; A.nw = P.nw; A.zalt = P.zalt; A.ym = P.ym;
+    A.f0r = P.f0r;
+    if (blk) {  // 3D blocks: x / y ghost layers from the faces after the trailing plane
+        A.blk = 1;
+        A.fy = g.n + g.plane;
+        A.fx = A.fy + 2 * p->nx * p->nz;
+        for (int sd = 2; sd < kHaloSides; ++sd)
+            if (block_nbr(c, sd) >= 0) A.nbm |= 1 << sd;
     }
-    // FD with F0 recomputed from u (2D, VEC <= 2: k_st2d<..., F0R>; 3D heat: k_st3l<..., F0R>, not
-    // with NK_F0R=3 (A/B)); never with the `fast` reciprocals,
-    // which would change F(u) against the residual kernel that stored F0.  NK_F0R: 1 (default) for the
-    // heat kinds, whose F(u) costs a few flops (8192^2 FD Jv 728 -> 612 us, bench +3.3 %), and for
-    // Bratu's Jv launches that also store V_k (fused normalisation): they move enough bytes to hide the
-    // second exp per point (config-4 slab Jv 277 -> 246 us, V_1 step 248 -> 227 us, bench +1.2 %),
-    // while the plain Jv + dot (116 -> 122 us) and the restart residual (110 -> 126 us) do not
-    // (profiles/r02/ab_f0r_bratu.log); 2 for every Bratu launch too; 0 never
-#ifndef NK_F0R_DEFAULT  // (product variant builds for A/B: 0 never, 2 every FD launch, 3 no 3D F0R)
-#define NK_F0R_DEFAULT 1
-#endif
-    static const int f0r_env = NK_TUNE("NK_F0R", NK_F0R_DEFAULT);
-    // 3D: the F0R kernel needs 145 VGPRs (3 waves per SIMD instead of 4), which pays only where the
-    // field is cheap and the kernel moves the most bytes: G_Euler!'s Jv with a dot partner (512^3
-    // FD Jv + V_k store 1400 -> 1198 us), not the V_1 = r0 / beta step, not midpoint / trapezoid
-    // (profiles/r02/ab_f0r3.log)
-    const bool dotvs = in.vout && in.epi == EPI_DOT && !in.aux;
-    const bool vfused = in.vout && in.epi == EPI_DOT;
-    const bool f0r = f0r_env && in.f0r && in.mode == MODE_JFD && vec <= 2 && !(fast & 1) &&
-                     ((g.dim == 2 && (f0r_env >= 2 || nk_is_heat(p->kind) || vfused)) ||
-                      (g.dim == 3 && A.lds3 && f0r_env != 3 && (f0r_env >= 2 || (p->kind == NK_HEAT3D_EULER && !dotvs))));
-    A.f0r = f0r ? 1 : 0;
-    if (in.xchg_v) {
-        // v's ghost planes: through the peers' inboxes inside this launch (halo_tile_exchange: only the
-        // tiles at the slab's ends fetch, the rest of the grid never waits) when the peer mailbox is up,
-        // the slab axis is not periodic and every tile of a plane has a flag; else exchanged first
-        const int fuse_env = halo_fuse_knob();
-        const int64_t tiles_pl = g.dim == 2 ? A.tiles_x : (int64_t)A.tiles_x * A.tiles_y;
-        const bool self = halo_self_ring(c);
-        // ranks sharing one GPU (rehearsals): in-launch only for small slabs -- a big slab's end tiles spin
-        // on CUs the peer's producing tiles need (r05: 8 ranks x 256^2 x 32 planes, 30.5 s per step fused;
-        // 26.7 ms with the exchange kernel, profiles/r06/rehearsal8_heat3d_256_slabs.json, the default
-        // spin limit).  Neighbours must agree on the form (tile flags vs
-        // the exchange kernel's block flags), so the test uses rank-uniform values only: the most ranks on
-        // one GPU and the slab size estimated from the global spacing, never this rank's slab
-        static const int64_t fuse_max = env_cfg("NK_SHARED_FUSE_MAX", 0) > 0 ? env_cfg("NK_SHARED_FUSE_MAX", 0) : kSharedFuseMax;
-        const bool share_ok = c->share_most <= 1 || shared_slab_points(c, p, g) <= fuse_max;
-        const bool fuse = fuse_env && c->mb_on && (c->nranks > 1 || self) && share_ok && !per && !A.blk && in.mode != MODE_RES &&
-                          (g.dim == 2 || (g.dim == 3 && A.lds3)) && g.plane <= c->halo_cap && tiles_pl <= kHaloTileFlags;
-        if (A.blk) {  // 3D blocks: k_faces_ipc first, or (opt-in) every ghost layer inside this launch
-            // In-launch (blk_tile_exchange) is bitwise the same but SLOWER on one GPU, the only place it can be
-            // measured here: the self-block 256^3 Jv 145 + 22 us (faces kernel) -> 187 us in-launch (2x2x2, every
-            // tile exchanges x patches and waits a round trip), 145 + 21 -> 172 us at 1x2x4 (profiles/r06/
-            // ab_blk_*.json).  NK_BLK_INLAUNCH=1 keeps it reachable for xGMI, where the separate kernel's
-            // transfer -- not a round trip -- would dominate (unmeasured)
-            static const int blk_in_env = env_cfg("NK_BLK_INLAUNCH", 0);
-            const bool bfuse = blk_in_env && fuse_env && c->mb_on && in.mode != MODE_RES && rows_override <= 0 &&
-                               blk_inlaunch_ok(c, p, fuse_max);
-            if (bfuse) {
-                ++c->n_jv_halo_fused;
-                A.hx_blk = 1;
-                A.hx_epoch = ++c->halo_epoch;
-                A.hx_cap = c->halo_cap;
-                for (int sd = 0; sd < kHaloSides; ++sd) A.bnbr[sd] = block_nbr(c, sd);
-                NK_TRY(blk_order(c, A, (int)((p->nz + A.rows - 1) / A.rows), &A.torder));
-            } else {
-                ++c->n_jv_halo_separate;
-                NK_TRY(halo_exchange(c, p, in.v));
-            }
-        } else if (fuse) {
-            ++c->n_jv_halo_fused;
-            A.hx_lo = c->rank > 0 || self;
-            A.hx_hi = c->rank + 1 < c->nranks || self;
-            A.hx_epoch = ++c->halo_epoch;
-            A.hx_cap = c->halo_cap;
-        } else {
-            if (c->nranks > 1 || per || self || block_self(c)) ++c->n_jv_halo_separate;
-            NK_TRY(halo_exchange(c, p, in.v));
-        }
+    const bool self = halo_self_ring(c);
+    switch (halo_form(c, in, g, P, blk, rows_override)) {  // v's ghost layers
+    case HALO_NONE: break;
+    case HALO_SEPARATE:
+        if (c->nranks > 1 || per || self || block_self(c)) ++c->n_jv_halo_separate;
+        NK_TRY(halo_exchange(c, p, in.v));
+        break;
+    case HALO_SLAB:
+        ++c->n_jv_halo_fused;
+        A.hx_lo = c->rank > 0 || self;
+        A.hx_hi = c->rank + 1 < c->nranks || self;
+        A.hx_epoch = ++c->halo_epoch;
+        A.hx_cap = c->halo_cap;
+        break;
+    case HALO_BLOCK:
+        ++c->n_jv_halo_fused;
+        A.hx_blk = 1;
+        A.hx_epoch = ++c->halo_epoch;
+        A.hx_cap = c->halo_cap;
+        for (int sd = 0; sd < kHaloSides; ++sd) A.bnbr[sd] = block_nbr(c, sd);
+        NK_TRY(blk_order(c, A, (int)((p->nz + A.rows - 1) / A.rows), &A.torder));
+        break;
     }
-    if (in.epi != EPI_NONE) {
-        int nparts = grid;
-        A.group = 1;
-        static const int tile_parts = std::max(1, std::min(kRedCap - 2, NK_TUNE("NK_TILE_PARTS", kTileParts)));
-        if (A.tile2 && grid > tile_parts) {  // one-shot tiles: about kTileParts group partials handed on
-            A.group = (grid + tile_parts - 1) / tile_parts;
-            nparts = (grid + A.group - 1) / A.group;
+    if (in.epi != EPI_NONE) {  // the reduction slot
+        A.group = P.group;
+        if (P.group > 1) {  // one-shot tiles: about kTileParts group partials handed on
             if (!c->tpart && hipMalloc(&c->tpart, sizeof(double) * (size_t)kTileCap) != hipSuccess)
                 return fail(c, NK_E_NOMEM, "one-shot tile partials");
             A.tpart = c->tpart;
         }
-        if (nparts > kRedCap - 2) return fail(c, NK_E_ARG, "stencil grid exceeds reduction capacity");
-        A.part = red_out(c, nparts, red, &A.fin);
+        if (P.nparts > kRedCap - 2) return fail(c, NK_E_ARG, "stencil grid exceeds reduction capacity");
+        A.part = red_out(c, P.nparts, red, &A.fin);
     }
-    // algorithmic (compulsory) bytes per launch, for the instantiation the dispatch launched (StInst: an
-    // F0R kernel reads no F0)
-    const bool heat = nk_is_heat(p->kind);
-    auto bytes_of = [&](const StInst& st) {
-        int words = 1;  // out
-        if (in.mode == MODE_RES) words += 1 + (heat ? 1 : 0);
-        else if (in.mode == MODE_JEXACT) words += 1 + (heat ? 0 : 1);
-        else words += 3 + (heat ? 1 : 0) - (st.f0r ? 1 : 0);
-        if (in.epi == EPI_RESID || (in.epi == EPI_DOT && in.aux)) words += 1;
-        if (in.vout) words += 1;  // fused kdivcopy!: V_k is written
-        return 8.0 * words * (double)g.n;
-    };
-    static const char* names[3][4] = {
-        {"residual", "residual_norm", "residual_dot", "residual_resid"},
-        {"jv_exact", "jv_exact_sumsq", "jv_exact_dot", "jv_exact_resid"},
-        {"jv_fd", "jv_fd_sumsq", "jv_fd_dot", "jv_fd_resid"}};
-    static const char* fused_names[3] = {"residual", "jv_exact_dot_norm", "jv_fd_dot_norm"};
-    static const char* v1_names[3] = {"residual", "jv_exact_dot_v1", "jv_fd_dot_v1"};
     if (in.vout && in.epi != EPI_DOT) return fail(c, NK_E_ARG, "fused normalisation needs the dot epilogue");
     // the kernels divide by h only in their V_k-storing instantiations (EPI_DOTV / EPI_DOTVS)
     if (in.vdiv && !in.vout) return fail(c, NK_E_ARG, "v / h is applied only with V_k stored (vout)");
-    const int kind = p->kind, mode = in.mode;
-    // distinct instantiations (own profile lines): normalise-and-store V_k, and its V_1 = r0/beta form
-    // whose dot partner is the stored vector itself
-    const int epi = (in.vout && in.epi == EPI_DOT) ? (in.aux ? EPI_DOTV : EPI_DOTVS) : in.epi;
+    const int kind = p->kind, mode = in.mode, vec = P.vec, grid = P.grid;
+    const int epi = vstore ? (in.aux ? EPI_DOTV : EPI_DOTVS) : in.epi;
     if (in.epi == EPI_DOT && !in.aux && !in.vout) return fail(c, NK_E_ARG, "dot epilogue needs its partner");
     hipStream_t s = c->stream;
-    const char* kname = epi == EPI_DOTV ? fused_names[mode] : (epi == EPI_DOTVS ? v1_names[mode] : names[mode][epi]);
+    const char* kname = epi == EPI_DOTV ? kStFusedNames[mode] : (epi == EPI_DOTVS ? kStV1Names[mode] : kStNames[mode][epi]);
     StInst st{};
     const char* stname = st.name;
     const int rc = launch_dyn(c, kname, [&] {
@@ -815,7 +723,7 @@ int launch_stencil_ex(nk_ctx* c, const StencilIn& in, Red* red, int rows_overrid
             const int ng = (grid + A.group - 1) / A.group;
             hipLaunchKernelGGL(k_tile_fold, dim3(ng), dim3(64), 0, s, A.tpart, A.group, grid, A.part, A.fin);
         }
-        return bytes_of(st);
+        return st_bytes(in, g.n, st);
     }, -1.0, &stname);
     if (rc == NK_OK && mode == MODE_JFD) ++(st.f0r ? c->n_fd_f0r : c->n_fd_f0_read);
     return rc;

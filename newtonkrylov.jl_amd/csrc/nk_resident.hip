@@ -29,14 +29,7 @@ namespace {
 // Double buffering is enough: a block can write pass t+2's granule only after reading everyone's
 // pass t+1 granule, i.e. after everyone finished reading pass t's.  Every spin is bounded.
 // Requires all G blocks co-resident: G = #CUs, 1 block per CU (the LDS share forces it).
-constexpr int kResMax = 64;  // passes per launch (reorthogonalisation: 2k)
-constexpr int kResThreads = 256;
-// tail-group size of a fully resident sweep (LDS slots; 0 = off): -DNK_RES_TAIL_DEFAULT=g for a `make variant`
-// A/B of the product build; the kbench build reads NK_RES_TAIL instead.
-#ifndef NK_RES_TAIL_DEFAULT
-#define NK_RES_TAIL_DEFAULT 24
-#endif
-constexpr int kResTail = NK_RES_TAIL_DEFAULT;
+// (kResMax passes per launch, kResThreads, the tail group's size kResTail and the residency rule: nk_plan.hpp)
 #ifdef NK_KBENCH
 int g_res_tail_hook = -1;     // nkb_mgs_res_tail: the tail size of its launches (overrides NK_RES_TAIL), -1 = none
 int g_res_tail_launched = 0;  // A.tg of the last launch
@@ -595,65 +588,140 @@ bool res_attr(size_t lds) {
 // this unit's copy of the mailbox binding (called by mailbox_bind)
 hipError_t resident_bind_mb(const MbInfo& m) { return hipMemcpyToSymbol(HIP_SYMBOL(g_mb), &m, sizeof(m)); }
 
+namespace {
+// one-time set-up of a context's resident path: the grid, the LDS slots, every instantiation's LDS
+// attribute, the granules and the error flag; anything missing turns the resident path off for good
+bool res_setup(nk_ctx* c) {
+    if (c->res_gran) return true;
+    int dev = 0, cus = 0, lds = 0;
+    bool ok = hipGetDevice(&dev) == hipSuccess &&
+              hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+              hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess &&
+              cus >= 1 && cus <= kResThreads;
+    if (ok) {
+        // ranks sharing this GPU (NK_RES_SHARED test rigs): each sweep grid gets its share of the CUs,
+        // so that all the ranks' grids are resident at once
+        c->res_blocks = std::max(1, cus / std::max(1, c->res_share));
+        const int avail = lds - (int)(sizeof(double) * kShN) - 256;
+        c->res_rl = std::max(0, avail / (int)(kResThreads * sizeof(dx2)));
+        const size_t lmax = (size_t)c->res_rl * kResThreads * sizeof(dx2);
+        ok = res_attr<0>(lmax) && res_attr<16>(lmax) && res_attr<25>(lmax) && res_attr<32>(lmax) && res_attr<48>(lmax) &&
+             res_attr<64>(lmax) && res_attr<89, 4, true>(lmax) && res_attr<89, 4, true, false, false, 0, true>(lmax);
+#ifdef NK_KBENCH
+        ok = ok && res_attr<89>(lmax) && res_attr<89, 4>(lmax) && res_attr<89, 6, false, true>(lmax) &&
+             res_attr<0, 8, false, true>(lmax) && res_attr<89, 6, false, false, true>(lmax) &&
+             res_attr<89, 6, false, false, false, 1>(lmax) && res_attr<89, 6, false, false, false, 2>(lmax) &&
+             res_attr<89, 6, false, false, false, 0, true>(lmax) && res_attr<89, 2, true>(lmax) &&
+             res_attr<89, 4, true, false, false, 0, false, 8>(lmax) &&
+             res_attr<89, 4, true, false, false, 0, false, 6>(lmax) && res_attr<89, 4, true, false, true>(lmax);
+#endif
+        int per_cu = 0;  // residency: at least one block of the largest variant per CU
+        ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                       &per_cu, reinterpret_cast<const void*>(&k_mgs_res<89, 4, true>), kResThreads, lmax) == hipSuccess &&
+             per_cu >= 1;
+    }
+    ok = ok && hipMalloc(&c->res_gran, sizeof(uint64_t) * 4 * kResThreads) == hipSuccess;
+    ok = ok && hipMemsetAsync(c->res_gran, 0, sizeof(uint64_t) * 4 * kResThreads, c->stream) == hipSuccess;
+    ok = ok && hipHostMalloc(&c->res_err, sizeof(int), hipHostMallocMapped) == hipSuccess;
+    if (ok) *c->res_err = 0;
+    ok = ok && hipHostGetDevicePointer(reinterpret_cast<void**>(&c->res_err_dev), c->res_err, 0) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        c->res_ok = false;
+    }
+    return ok;
+}
+
+// the plan's knobs: read once per process, NK_RES_MIRROR and the bench hook's tail at every launch
+ResKnobs res_knobs() {
+    static const ResKnobs once = [] {
+        const ResKnobs D;
+        ResKnobs K;
+        K.rl = NK_TUNE("NK_RES_RL", D.rl);
+        K.rv = NK_TUNE("NK_RES_RV", D.rv);
+        K.nts = NK_TUNE("NK_RES_NTS", D.nts);
+        K.pre = NK_TUNE("NK_RES_PRE", D.pre);
+        K.vout = NK_TUNE("NK_RES_VOUT", D.vout);
+        K.strided = NK_TUNE("NK_RES_STRIDED", D.strided);
+        K.tail = NK_TUNE("NK_RES_TAIL", D.tail);
+        K.ntc = NK_TUNE("NK_RES_NTC", D.ntc);
+        K.mall_mb = NK_TUNE("NK_RES_MALL_MB", D.mall_mb);
+        K.jv = NK_TUNE("NK_RES_JV", D.jv);
+        return K;
+    }();
+    ResKnobs K = once;
+    K.mirror = NK_TUNE("NK_RES_MIRROR", K.mirror);
+#ifdef NK_KBENCH
+    if (g_res_tail_hook >= 0) K.tail = g_res_tail_hook;
+#endif
+    return K;
+}
+
+// launch the instantiation the plan names.  Load policy of the 89-slot variants (kbench: NK_RES_NTS /
+// NK_RES_PRE): with a streamed remainder its q and V_{i+1} go non-temporal, so the Infinity Cache keeps
+// the resident part's V_{i+1} for the next pass (kbench_res: -2..3 % per pass at half residency, -2..7 %
+// at a quarter; config-4 slab bench +2.4 %, heat 8192^2 +3.9 %); batches of 4 with the first one loaded
+// across the hand-off (-1.5 % per pass at k = 30, full residency; 4096^2 bench +0.6 %).  Same per-element
+// arithmetic and accumulation order in every variant: bit-identical results.
+const char* res_dispatch(const ResPlan& P, const ResKnobs& K, [[maybe_unused]] bool jv, dim3 g, dim3 b, size_t lds,
+                         hipStream_t s, const ResArgs& A) {
+#define NK_GO_RES(...) return go_res<__VA_ARGS__>(g, b, lds, s, A)
+    const bool nts = !P.full && K.nts;
+#ifdef NK_KBENCH  // the instantiations only the kernel-variant build has
+    if (jv && P.rv == 0) NK_GO_RES(0, 8, false, true);
+    if (jv) NK_GO_RES(89, 6, false, true);
+    if (P.rv == 89) {
+        switch (P.xv) {
+        case 1: NK_GO_RES(89, 4);
+        case 2: NK_GO_RES(89, 6, false, false, true);
+        case 3: NK_GO_RES(89, 6, false, false, false, 1);
+        case 4: NK_GO_RES(89, 6, false, false, false, 2);
+        case 5: NK_GO_RES(89, 6, false, false, false, 0, true);
+        case 8: NK_GO_RES(89, 2, true);
+        case 9: NK_GO_RES(89, 4, true, false, false, 0, false, 8);
+        case 10: NK_GO_RES(89, 4, true, false, false, 0, false, 6);
+        case 11: NK_GO_RES(89, 4, true, false, true);
+        default: break;
+        }
+        if (P.xv != 0 && P.xv != 6 && !K.pre) {
+            if (nts) NK_GO_RES(89, 6, false, false, false, 0, true);
+            NK_GO_RES(89);
+        }
+    }
+#endif
+    switch (P.rv) {
+    case 0: NK_GO_RES(0);
+    case 16: NK_GO_RES(16);
+    case 25: NK_GO_RES(25);
+    case 48: NK_GO_RES(48);
+    case 64: NK_GO_RES(64);
+    case 89:
+        if (P.xv == 6 || (P.xv != 0 && nts)) NK_GO_RES(89, 4, true, false, false, 0, true);
+        NK_GO_RES(89, 4, true);
+    default: NK_GO_RES(32);
+    }
+#undef NK_GO_RES
+}
+}  // namespace
 
 // Resident sweep: returns NK_OK after enqueueing, or 1 when the resident path does not apply
 // (caller falls back to one k_mgs_pass launch per pass).
 int launch_mgs_sweep(nk_ctx* c, int64_t n, double* q, const double* const* V, int k, int np, Red in, double* col,
                      double* colh, int rv, double** vout, const ResJv* jin) {
-    if (np < 1 || np > kResMax || (n & 1) || !c->res_ok) return 1;
+    if (!c->res_ok || (c->comm && !c->mb_on)) return 1;  // RCCL reductions need the host between passes
+    if (!res_setup(c)) return 1;
+    const ResKnobs K = res_knobs();
+    const ResPlan P = res_plan(n, np, c->res_blocks, c->res_rl, rv, vout && *vout, jin ? jin->nx : 0, K);
+    if (!P.applies) return 1;
+    if (vout && *vout && !P.keep_vout) *vout = nullptr;
 #ifdef NK_KBENCH
-    // fused Jv phase (kbench build only): at one wave per SIMD its ~190 fp64 VALU instructions per
-    // point pair (IEEE divisions, two exp) do not hide behind the loads: 791 us per Arnoldi step vs
-    // 619 + 124 us for the sweep and a separate Jv kernel (-1.7 % end to end, 4096^2)
-    static const int jv_env = NK_TUNE("NK_RES_JV", 0);
-    if (jin && (!jv_env || !vout || !*vout || jin->nx % 2 != 0)) return 1;
-#else
-    if (jin) return 1;
+    g_res_tail_launched = P.tg;
 #endif
-    if (c->comm && !c->mb_on) return 1;  // RCCL reductions need the host between passes
-    if (!c->res_gran) {  // one-time set-up; anything missing turns the resident path off for good
-        int dev = 0, cus = 0, lds = 0;
-        bool ok = hipGetDevice(&dev) == hipSuccess &&
-                  hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-                  hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess &&
-                  cus >= 1 && cus <= kResThreads;
-        if (ok) {
-            // ranks sharing this GPU (NK_RES_SHARED test rigs): each sweep grid gets its share of the CUs,
-            // so that all the ranks' grids are resident at once
-            c->res_blocks = std::max(1, cus / std::max(1, c->res_share));
-            const int avail = lds - (int)(sizeof(double) * kShN) - 256;
-            c->res_rl = std::max(0, avail / (int)(kResThreads * sizeof(dx2)));
-            const size_t lmax = (size_t)c->res_rl * kResThreads * sizeof(dx2);
-            ok = res_attr<0>(lmax) && res_attr<16>(lmax) && res_attr<25>(lmax) && res_attr<32>(lmax) && res_attr<48>(lmax) &&
-                 res_attr<64>(lmax) && res_attr<89, 4, true>(lmax) && res_attr<89, 4, true, false, false, 0, true>(lmax);
-#ifdef NK_KBENCH
-            ok = ok && res_attr<89>(lmax) && res_attr<89, 4>(lmax) && res_attr<89, 6, false, true>(lmax) &&
-                 res_attr<0, 8, false, true>(lmax) && res_attr<89, 6, false, false, true>(lmax) &&
-                 res_attr<89, 6, false, false, false, 1>(lmax) && res_attr<89, 6, false, false, false, 2>(lmax) &&
-                 res_attr<89, 6, false, false, false, 0, true>(lmax) && res_attr<89, 2, true>(lmax) &&
-                 res_attr<89, 4, true, false, false, 0, false, 8>(lmax) &&
-                 res_attr<89, 4, true, false, false, 0, false, 6>(lmax) && res_attr<89, 4, true, false, true>(lmax);
-#endif
-            int per_cu = 0;  // residency: at least one block of the largest variant per CU
-            ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                           &per_cu, reinterpret_cast<const void*>(&k_mgs_res<89, 4, true>), kResThreads, lmax) == hipSuccess &&
-                 per_cu >= 1;
-        }
-        ok = ok && hipMalloc(&c->res_gran, sizeof(uint64_t) * 4 * kResThreads) == hipSuccess;
-        ok = ok && hipMemsetAsync(c->res_gran, 0, sizeof(uint64_t) * 4 * kResThreads, c->stream) == hipSuccess;
-        ok = ok && hipHostMalloc(&c->res_err, sizeof(int), hipHostMallocMapped) == hipSuccess;
-        if (ok) *c->res_err = 0;
-        ok = ok && hipHostGetDevicePointer(reinterpret_cast<void**>(&c->res_err_dev), c->res_err, 0) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            c->res_ok = false;
-            return 1;
-        }
-    }
     ResArgs A{};
     for (int t = 0; t < np; ++t) A.V[t] = V[t % k];
     A.V[np] = V[(np) % k];
     A.q = q;
+    A.vout = vout ? *vout : nullptr;
     A.col = col;
     A.colh = colh;
     A.red_in = in.ptr;
@@ -662,79 +730,11 @@ int launch_mgs_sweep(nk_ctx* c, int64_t n, double* q, const double* const* V, in
     A.err = c->res_err_dev;
     A.n2 = n >> 1;
     A.np = np;
-    // load policy (kbench: NK_RES_NTS / NK_RES_PRE): with a streamed remainder its q and V_{i+1} go
-    // non-temporal, so the Infinity Cache keeps the resident part's V_{i+1} for the next pass (kbench_res:
-    // -2..3 % per pass at half residency, -2..7 % at a quarter; config-4 slab bench +2.4 %, heat 8192^2
-    // +3.9 %); batches of 4 with the first one loaded across the hand-off (-1.5 % per pass at k = 30,
-    // full residency; 4096^2 bench +0.6 %).  Same per-element arithmetic and accumulation order in every
-    // variant: bit-identical results.
-    static const int nts_env = NK_TUNE("NK_RES_NTS", 1);
-    static const int pre_env = NK_TUNE("NK_RES_PRE", 1);
-    int xv = -1;  // experimental variant (kbench build)
-    bool streamed = false;  // part of q streams through memory (partial residency)
-    {  // every block's chunk must hold its rv + rl resident slots in full (the kernel does not predicate them)
-        const int64_t G = c->res_blocks, n2 = n >> 1;
-        const int64_t ns = (n2 + kResThreads - 1) / kResThreads;
-        const int64_t whole = ns / G - (n2 % kResThreads != 0 ? 1 : 0);  // the last block's last slot may be partial
-        if (whole < 1) return 1;
-        const int slots = (int)std::min<int64_t>(whole, 1 << 20);
-        static const int rl_env = NK_TUNE("NK_RES_RL", -1);
-        static const int rv_env = NK_TUNE("NK_RES_RV", -1);
-        int rl = std::min(slots, rl_env >= 0 ? std::min(rl_env, c->res_rl) : c->res_rl);  // LDS first
-        const bool explicit_rv = rv >= 0 || rv_env >= 0;  // a caller's choice skips the benefit test below
-#ifdef NK_KBENCH
-        if (rv >= 1000) {  // kernel-variant bench: 1000 + {0: 89 slots, batches of 4 + prefetch across the hand-off; 1: same, no prefetch; 2: alternating slot order; 3: V_i cached; 4: V_{i+1} non-temporal; 5: streamed remainder non-temporal (NTS); 6: 0 + 5; 8: batches of 2 + prefetch (batches of 6 + prefetch spill); 9 / 10: 0 with LDS slots in batches of 8 / 6; 11: 0 with alternate passes starting on the top LDS group (prefetched across the hand-off)}
-            xv = rv - 1000;
-            rv = 89;
-        }
-#endif
-        if (rv < 0) rv = rv_env >= 0 ? rv_env : slots - rl;  // registers hold what the LDS cannot
-        // the instantiated register-slot counts (25 + 39 LDS slots = 64: a 4096 x 2048 slab, 4096^2 on two GPUs)
-        static const int kRv[] = {89, 64, 48, 32, 25, 16, 0};
-        int pick = 0;
-        for (int r : kRv)
-            if (r <= rv && r <= slots) {
-                pick = r;
-                break;
-            }
-        if (xv < 0) rv = pick;
-        else if (rv > slots) return 1;
-        A.rl = std::min(rl, slots - rv);
-        if (xv == 11 && A.rl < 4) xv = 0;  // ALT + prefetch starts on the top LDS group of 4
-        // worth it from two passes on (a one-pass sweep only adds q's load + store) while a tenth of q
-        // or more is resident (tools/kbench_res.py per pass vs the chain: 4096^2 1.28x at k = 2,
-        // 1.8x from k = 16; 2 x 4096^2 (half resident) 1.40-1.52x; 8192^2 (a quarter) 1.16-1.18x;
-        // 512^3 (an eighth) 1.06-1.09x -- with the streamed remainder non-temporal; 1.01x at 512^3
-        // without it, hence a fifth then)
-        const int64_t chunk = std::max<int64_t>(1, ns / G);
-        const double f = (double)(rv + A.rl) / (double)chunk;  // resident fraction of q
-        if (!explicit_rv && (np < 2 || f < (nts_env ? 0.1 : 0.2))) return 1;
-        // V_{k+1} straight from the registers only when all of q is resident (no streamed slot; a
-        // partial last slot is streamed)
-        const bool full = n2 % kResThreads == 0 && (ns + G - 1) / G <= rv + A.rl;
-        streamed = !full;
-        static const int vout_env = NK_TUNE("NK_RES_VOUT", 1);
-        if (vout && *vout && !(full && vout_env)) *vout = nullptr;
-        A.vout = vout ? *vout : nullptr;
-        if (jin && (!A.vout || (rv != 0 && rv != 89) || (rv > 0 && A.rl < 16))) return 1;  // fused Jv: full residency, instantiated rv, LDS staging
-        // slots interleaved across the blocks (kbench): a different partition of the partial sums
-        static const int strided_env = NK_TUNE("NK_RES_STRIDED", 0);
-        A.strided = strided_env && n2 % kResThreads == 0 && ns % G == 0 && ns / G == rv + A.rl;
-        A.mirror = NK_TUNE("NK_RES_MIRROR", 0) && !A.strided && n2 % kResThreads == 0 && ns % G == 0 && ns / G == rv + A.rl;
-        // tail group: only where all of q is resident -- the streamed remainder follows the
-        // LDS slots in the chain of partial sums and loads between the tail's two phases -- and never
-        // with the alternating slot orders (kbench variants 2 and 11), which end a pass elsewhere
-        static const int tail_env = NK_TUNE("NK_RES_TAIL", kResTail);
-        int tail = tail_env;
-#ifdef NK_KBENCH
-        if (g_res_tail_hook >= 0) tail = g_res_tail_hook;
-#endif
-        A.tg = full && xv != 2 && xv != 11 ? std::max(0, std::min(tail, A.rl)) : 0;
-#ifdef NK_KBENCH
-        g_res_tail_launched = A.tg;
-#endif
-    }
-#ifdef NK_KBENCH
+    A.rl = P.rl;
+    A.tg = P.tg;
+    A.strided = P.strided;
+    A.mirror = P.mirror;
+    A.ntc = P.ntc;
     if (jin) {
         A.jv_on = 1;
         A.ju = jin->u;
@@ -747,7 +747,6 @@ int launch_mgs_sweep(nk_ctx* c, int64_t n, double* q, const double* const* V, in
         A.jhy2 = jin->hy2;
         A.jnx = jin->nx;
     }
-#endif
     const unsigned nx_ = (unsigned)np + (jin ? 1u : 0u);  // hand-offs in this launch
     if (c->res_tag > 0xfffffff0u - (unsigned)(kResMax + 1)) {  // tag wrap: restart from clean granules
         NK_HIP(c, hipMemsetAsync(c->res_gran, 0, sizeof(uint64_t) * 4 * kResThreads, c->stream));
@@ -761,20 +760,7 @@ int launch_mgs_sweep(nk_ctx* c, int64_t n, double* q, const double* const* V, in
         A.mb0 = c->mb_epoch + 1;
         c->mb_epoch += nx_;
     }
-#ifdef NK_KBENCH
-    A.noxchg = NK_TUNE("NK_RES_NOXCHG", 0);  // timing probe only: the h exchange skipped (wrong results)
-#endif
-    // NTS: the Infinity Cache (256 MB) keeps the resident part's V_{i+1} (4 KB per block and slot) for
-    // its re-read as the next pass's V_i; the room left (244 MB of it) goes to the first streamed slots
-    // of every block, whose V_{i+1} then loads cached: half resident 129.3 -> 120.2 us per pass, a
-    // quarter 313.1 -> 300.1 (profiles/r02/ab_ntc.log; 128 slots, past the room, thrash)
-    static const int ntc_env = NK_TUNE("NK_RES_NTC", -1);
-    static const int mall_mb = NK_TUNE("NK_RES_MALL_MB", 244);
-    {
-        const double slot = 4096.0 * c->res_blocks;  // one slot of V across the grid, bytes
-        const double room = 1e6 * mall_mb - slot * (rv + A.rl);
-        A.ntc = ntc_env >= 0 ? ntc_env : (room > 0 ? (int)(room / slot) : 0);
-    }
+    A.noxchg = NK_TUNE("NK_RES_NOXCHG", 0);  // kbench timing probe only: the h exchange skipped (wrong results)
     A.poll1 = NK_TUNE("NK_RES_POLL1", 1);
     A.nwc = NK_TUNE("NK_RES_NWC", 1 << 30);
     A.tstamp = c->res_tstamp;
@@ -785,62 +771,12 @@ int launch_mgs_sweep(nk_ctx* c, int64_t n, double* q, const double* const* V, in
     A.senders = std::max(1, std::min(senders, c->res_blocks));
     A.spin = 1u << 22;  // polls per thread per launch (~1 s): a grid that is not co-resident fails fast
     const size_t lds = (size_t)A.rl * kResThreads * sizeof(dx2);
-    // algorithmic bytes: the resident fraction f of q is loaded once (or computed by the fused Jv
-    // from u, V_k, F0, V_1), stored once (q or V_{k+1}) and each pass reads V_i (+ V_{i+1}); the
-    // streamed rest reads and writes q in every pass as well (k_mgs_pass's 32 / 24 B/pt)
-    const double f = std::min(1.0, (double)c->res_blocks * (rv + A.rl) * kResThreads / (double)(n >> 1));
-    const double per_res = (jin ? 5.0 : 2.0) + 2.0 * np - 1.0, per_str = 4.0 * np - 1.0;  // doubles per point
-    const double bytes = 8.0 * (double)n * (f * per_res + (1.0 - f) * per_str);
-    // unique-DRAM model: V_{i+1}, read again as the next pass's V_i, counted once (the Infinity Cache
-    // serves the second read at best): np + 2 doubles per resident point (q in, V_1..V_np, q / V_{k+1}
-    // out), 3 np for a streamed point (q read and written every pass, each V once)
-    const double dram = 8.0 * (double)n * (f * ((jin ? 5.0 : 2.0) + np) + (1.0 - f) * (3.0 * np));
     ++c->n_sweep_resident;
     const char* kn = nullptr;
     return launch_dyn(c, jin ? "arnoldi_step" : "mgs_sweep", [&] {
-        const dim3 g(c->res_blocks), b(kResThreads);
-        switch (rv) {
-        case 0:
-#ifdef NK_KBENCH
-            if (jin) kn = go_res<0, 8, false, true>(g, b, lds, c->stream, A);
-            else
-#endif
-                kn = go_res<0>(g, b, lds, c->stream, A);
-            break;
-        case 16: kn = go_res<16>(g, b, lds, c->stream, A); break;
-        case 25: kn = go_res<25>(g, b, lds, c->stream, A); break;
-        case 48: kn = go_res<48>(g, b, lds, c->stream, A); break;
-        case 64: kn = go_res<64>(g, b, lds, c->stream, A); break;
-        case 89:
-#ifdef NK_KBENCH
-            if (jin) kn = go_res<89, 6, false, true>(g, b, lds, c->stream, A);
-            else if (xv == 0) kn = go_res<89, 4, true>(g, b, lds, c->stream, A);
-            else if (xv == 1) kn = go_res<89, 4>(g, b, lds, c->stream, A);
-            else if (xv == 2) kn = go_res<89, 6, false, false, true>(g, b, lds, c->stream, A);
-            else if (xv == 3) kn = go_res<89, 6, false, false, false, 1>(g, b, lds, c->stream, A);
-            else if (xv == 4) kn = go_res<89, 6, false, false, false, 2>(g, b, lds, c->stream, A);
-            else if (xv == 5) kn = go_res<89, 6, false, false, false, 0, true>(g, b, lds, c->stream, A);
-            else if (xv == 6) kn = go_res<89, 4, true, false, false, 0, true>(g, b, lds, c->stream, A);
-            else if (xv == 8) kn = go_res<89, 2, true>(g, b, lds, c->stream, A);
-            else if (xv == 9) kn = go_res<89, 4, true, false, false, 0, false, 8>(g, b, lds, c->stream, A);
-            else if (xv == 10) kn = go_res<89, 4, true, false, false, 0, false, 6>(g, b, lds, c->stream, A);
-            else if (xv == 11) kn = go_res<89, 4, true, false, true>(g, b, lds, c->stream, A);
-            else if (streamed && nts_env && pre_env)
-                kn = go_res<89, 4, true, false, false, 0, true>(g, b, lds, c->stream, A);
-            else if (streamed && nts_env) kn = go_res<89, 6, false, false, false, 0, true>(g, b, lds, c->stream, A);
-            else if (pre_env) kn = go_res<89, 4, true>(g, b, lds, c->stream, A);
-            else kn = go_res<89>(g, b, lds, c->stream, A);
-#else
-            (void)xv;
-            (void)pre_env;
-            if (streamed) kn = go_res<89, 4, true, false, false, 0, true>(g, b, lds, c->stream, A);
-            else kn = go_res<89, 4, true>(g, b, lds, c->stream, A);
-#endif
-            break;
-        default: kn = go_res<32>(g, b, lds, c->stream, A); break;
-        }
-        return bytes;
-    }, dram, &kn);
+        kn = res_dispatch(P, K, jin != nullptr, dim3(c->res_blocks), dim3(kResThreads), lds, c->stream, A);
+        return P.bytes;
+    }, P.dram, &kn);
 }
 
 }  // namespace nk

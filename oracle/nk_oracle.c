@@ -473,7 +473,7 @@ static double dr_chunk(int64_t n, const double* x, const double* y, int64_t G) {
     free(parts);
     return r;
 }
-/* k_st2d's tile geometry (launch_stencil_ex, nk_kernels.hip: about 1024 tiles of 8 .. 32 rows) */
+/* k_st2d's tile geometry (st_plan, csrc/nk_plan.hpp: about 1024 tiles of 8 .. 32 rows) */
 static void dr_tiles2d(int64_t nx, int64_t ny, int* vec, int64_t* tiles_x, int64_t* rows, int64_t* tiles_y) {
     *vec = nx % 2 == 0 ? 2 : 1;
     *tiles_x = (nx + 256 * *vec - 1) / (256 * *vec);
@@ -509,7 +509,7 @@ int64_t oc_dr_tile_parts2d(int64_t nx, int64_t ny, const double* x, const double
     }
     return tx_n * ty_n;
 }
-/* k_st3l's tiles (launch_stencil_ex, nk_kernels.hip): 4 rows (one per wave) x 64 VEC columns, z-chunks of
+/* k_st3l's tiles (st_plan, csrc/nk_plan.hpp): 4 rows (one per wave) x 64 VEC columns, z-chunks of
  * `planes` (blocks: 16; else about 8192 tiles, at least 16), partial index tz tiles_x tiles_y + ty tiles_x + tx;
  * thread (wave w, lane l) sums its VEC points of row ty 4 + w plane by plane upward */
 int64_t oc_dr_tile_parts3d(int64_t nx, int64_t ny, int64_t nz, int blk, const double* x, const double* y, double* parts) {
@@ -562,7 +562,7 @@ static double dr_tiles_local(int dim, int64_t nx, int64_t ny, int64_t nz, int bl
     free(parts);
     return r;
 }
-/* the resident sweep (launch_mgs_sweep, nk_resident.hip): does it run for np passes over n points? */
+/* the resident sweep (res_plan, csrc/nk_plan.hpp): does it run for np passes over n points? */
 static int dr_sweep_applies(int64_t n, int np) {
     if (np < 2 || np > 64 || (n & 1)) return 0;
     const int64_t G = OC_DEV_CUS, n2 = n >> 1, ns = (n2 + 255) / 256;
@@ -578,6 +578,10 @@ static int dr_sweep_applies(int64_t n, int np) {
     const int64_t chunk = ns / G > 1 ? ns / G : 1;
     return (double)(rv + rl) / (double)chunk >= 0.1;
 }
+/* the rules above as the tests compare them with csrc/nk_plan.hpp (tests/test_plan.py) */
+int oc_dr_sweep_applies(int64_t n, int np) { return dr_sweep_applies(n, np); }
+int64_t oc_dr_red_blocks(int64_t n) { return dr_red_blocks(n); }
+int64_t oc_dr_wide_blocks(int64_t n) { return dr_wide_blocks(n); }
 void oc_dr_sweep_parts(int64_t n, const double* x, const double* y, int64_t G, double* parts) {
     if (!y) y = x;
     const int64_t n2 = n >> 1, ns = (n2 + 255) / 256;

@@ -131,6 +131,14 @@ def lib():
         L.oc_dr_sweep_parts.argtypes = [I64, P, P, I64, P]
         L.oc_dr_tile_parts2d.argtypes = [I64, I64, P, P, P]
         L.oc_dr_tile_parts2d.restype = I64
+        L.oc_dr_tile_parts1d.argtypes = [I64, P, P, P]
+        L.oc_dr_tile_parts1d.restype = I64
+        L.oc_dr_sweep_applies.argtypes = [I64, C.c_int]
+        L.oc_dr_sweep_applies.restype = C.c_int
+        L.oc_dr_red_blocks.argtypes = [I64]
+        L.oc_dr_red_blocks.restype = I64
+        L.oc_dr_wide_blocks.argtypes = [I64]
+        L.oc_dr_wide_blocks.restype = I64
         L.oc_get_threads.restype = C.c_int
         for name in ("oc_axpy",):
             getattr(L, name).argtypes = [I64, D, P, P]

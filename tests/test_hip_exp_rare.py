@@ -150,7 +150,7 @@ def plant2d(nx, ny):
     one); (d) the quiet patch: rows 6..9 over the full width, distinct family values; (e) 16 fixture values
     at seeded interior points."""
     P = oc.bratu2d(nx, ny)
-    assert 8 < ny <= 64  # 8-row tiles (launch_stencil_ex's floor), at least two of them
+    assert 8 < ny <= 64  # 8-row tiles (st_plan's floor, csrc/nk_plan.hpp), at least two of them
     rng = np.random.default_rng(1000 * nx + ny)
     u = oc.sin_ic(P) + 0.05 * rng.standard_normal(P.shape)
     pool = iter(rng.permutation(np.arange(FAM_LO + KMAX, FAM_LO + FAM_N - KMAX)))

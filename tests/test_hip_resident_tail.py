@@ -1,13 +1,14 @@
-"""The tail group of the fully resident MGS sweep (k_mgs_res / launch_mgs_sweep in csrc/nk_resident.hip).
+"""The tail group of the fully resident MGS sweep (k_mgs_res in csrc/nk_resident.hip).
 
 With a tail group of tg slots a pass runs in three phases: the last tg LDS slots are updated first (q -= h V_i, on
 the lines the previous pass loaded last), then the register slots and the remaining LDS slots run the fused update +
 dot as before, then the tail's dot runs, in slot order.  Only the order of the elementwise updates moves: the chain of
 partial sums is the one of the schedule without a tail, so every result is the same bits.
 
-`tail_plan` restates the host rule next to a copy of `sweep_plan`; a CPU test holds every case of the table against
-the geometry it names (256 blocks, 39 LDS slots).  Each GPU case runs in a child process on the kernel-variant build
-with NK_RES_TAIL=16, whatever size the product compiles in: short restarted GMRES solves (memory 8, itmax 12: sweeps of
+`tail_plan` restates the host rule (res_plan, csrc/nk_plan.hpp) on top of test_hip_resident_variants.py's `sweep_plan`;
+a CPU test holds every case of the table against the geometry it names (256 blocks, 39 LDS slots), and
+tests/test_plan.py holds both restatements against the product's rule.  Each GPU case runs in a child process on the
+kernel-variant build with NK_RES_TAIL=16, whatever size the product compiles in: short restarted GMRES solves (memory 8, itmax 12: sweeps of
 2 to 8 passes, 2 to 16 with reorthogonalisation), plain and with reorthogonalisation, the history and x bit for bit
 against the oracle in device order (test_hip_resident_variants.py's harness), the tail the rule predicts launched,
 every step of two passes or more resident.  A one-pass step (the first of a cycle without reorthogonalisation) takes
@@ -26,29 +27,20 @@ import pytest
 import _nkpath  # noqa: F401
 from ariadne_hip import _lib
 
-K_RES_MAX = 64  # kResMax of nk_resident.hip
-RV_SET = (89, 64, 48, 32, 25, 16, 0)  # kRv
-SLOT = 256  # kResThreads
+from test_hip_resident_variants import K_RES_MAX, sweep_plan, whole_slots
+
 G_TEST = 16  # the configured tail of the GPU cases (NK_RES_TAIL)
-
-
-def sweep_plan(n, G=256, rl=39):
-    """launch_mgs_sweep's selection for n doubles on G blocks with rl LDS slots: (whole, rv, rl, full)."""
-    n2 = n // 2
-    ns = -(-n2 // SLOT)
-    whole = ns // G - (n2 % SLOT != 0)
-    if whole < 1:
-        return None
-    rl = min(whole, rl)  # LDS first
-    rv = next(r for r in RV_SET if r <= whole - rl)  # registers hold what the LDS cannot
-    full = n2 % SLOT == 0 and -(-ns // G) <= rv + rl
-    return whole, rv, rl, full
 
 
 def tail_plan(n, g, G=256, rl=39):
     """The host rule: the tail is the configured g clamped to the LDS slots in use, and only at full residency."""
-    whole, rv, rl, full = sweep_plan(n, G, rl)
+    rv, rl, full, _, _ = sweep_plan(n, G, rl)
     return min(g, rl) if full and g > 0 else 0
+
+
+def geometry(n):
+    """(whole, rv, rl, full) of n doubles on 256 blocks with 39 LDS slots."""
+    return (whole_slots(n),) + sweep_plan(n)[:3]
 
 
 def sweep_steps(itmax, memory, reorth):
@@ -78,14 +70,14 @@ def case_id(c):
 
 def test_cases_reach_the_geometry_they_name():
     for c in CASES:
-        assert sweep_plan(c.nx * c.ny) == (c.whole, c.rv, c.rl, c.full), c
+        assert geometry(c.nx * c.ny) == (c.whole, c.rv, c.rl, c.full), c
         assert tail_plan(c.nx * c.ny, G_TEST) == c.tg, c
         assert c.rl - c.tg == c.fused, c
         assert tail_plan(c.nx * c.ny, 0) == 0
     assert [c.fused % 4 for c in CASES[2:4]] == [1, 3]  # fused loops that end in single slots
     assert sum(1 for c in CASES if c.full and c.fused == 0) == 2 and sum(1 for c in CASES if not c.full) == 1
     # the kbench case: what the rule predicts for each tail at its two shapes (4096^2: rv 89 + 39 LDS slots)
-    assert sweep_plan(4096 * 4096) == (128, 89, 39, True)
+    assert geometry(4096 * 4096) == (128, 89, 39, True)
     assert [tail_plan(2048 * 1856, t) for t in KBENCH_TAILS] == [0, 8, 16, 24]
     assert [tail_plan(4096 * 4096, t) for t in KBENCH_TAILS + (64,)] == [0, 8, 16, 24, 39]
     # passes per launch: 2 .. 8 plain, 2 .. 16 with reorthogonalisation, 64 = kResMax at GMRES(32)

@@ -1,4 +1,5 @@
-"""Every register-slot variant of the resident MGS sweep (launch_mgs_sweep / k_mgs_res in csrc/nk_resident.hip).
+"""Every register-slot variant of the resident MGS sweep (k_mgs_res in csrc/nk_resident.hip; the selection rule is
+res_plan in csrc/nk_plan.hpp).
 
 The host picks the register slots rv from {89, 64, 48, 32, 25, 16, 0} by the vector length alone, and each value is
 an instantiation of its own with its own unrolled register loops.  test_hip_resident.py and test_hip.py reach rv = 0,
@@ -8,8 +9,8 @@ Jacobi N (it writes q back), and with a streamed remainder whose last slot is pa
 one selection threshold (the last slot count of 25 against the first of 32), and the pass-count edge: a sweep of
 exactly kResMax = 64 passes and a cycle that crosses it and falls back to the per-pass chain.
 
-`sweep_plan` restates the host's selection rule; a CPU test holds every case against the variant and geometry it
-names, so the cases stay honest if a shape is edited.  Each GPU case then asserts that the variant ran (the profile's
+`sweep_plan` restates the host's selection rule (tests/test_plan.py holds it against res_plan itself); a CPU test holds
+every case against the variant and geometry it names, so the cases stay honest if a shape is edited.  Each GPU case then asserts that the variant ran (the profile's
 kernel name), the history and x bit for bit against the oracle in device order, against the plain-order oracle to
 test_resident_sweep_matches_oracle's tolerances, the true residual of the device's x (host Jv) against the estimate
 and the orthonormality of the last cycle's basis (test_full_size_cycle_properties's tolerances).
@@ -23,7 +24,7 @@ import _nkpath  # noqa: F401
 import ariadne_hip as ah
 from oracle import oracle as oc
 
-K_RES_MAX = 64  # kResMax of nk_resident.hip: passes per resident launch
+K_RES_MAX = 64  # kResMax of nk_plan.hpp: passes per resident launch
 RV_SET = (89, 64, 48, 32, 25, 16, 0)  # kRv: the instantiated register-slot counts
 SLOT = 256  # kResThreads: double2 elements per slot
 
@@ -36,7 +37,7 @@ def whole_slots(n, G=256):
 
 
 def sweep_plan(n, G=256, rl=39):
-    """launch_mgs_sweep's selection for a vector of n doubles on G blocks with rl LDS slots available:
+    """res_plan's selection for a vector of n doubles on G blocks with rl LDS slots available:
     (rv, rl, full, partial_last_slot, ragged_blocks); None where no block holds a whole slot."""
     n2 = n // 2
     ns = -(-n2 // SLOT)
@@ -47,6 +48,15 @@ def sweep_plan(n, G=256, rl=39):
     rv = next(r for r in RV_SET if r <= whole - rl)  # registers hold what the LDS cannot
     full = n2 % SLOT == 0 and -(-ns // G) <= rv + rl
     return rv, rl, full, n2 % SLOT != 0, ns % G != 0
+
+
+def sweep_applies(n, np_, G=256, rl=39):
+    """Does a sweep of np_ passes over n doubles run resident?  2 to kResMax passes (a one-pass sweep only adds q's
+    load and store), an even n, a whole slot in every block, and a tenth of a block's chunk or more resident."""
+    plan = sweep_plan(n, G, rl)
+    if not 2 <= np_ <= K_RES_MAX or n % 2 or plan is None:
+        return False
+    return (plan[0] + plan[1]) / max(1, -(-(n // 2) // SLOT) // G) >= 0.1
 
 
 def sweep_steps(itmax, memory, reorth):
