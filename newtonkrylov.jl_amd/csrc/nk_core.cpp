@@ -184,6 +184,16 @@ void prof_drain(nk_ctx* c, bool blocking) {
     c->pending.erase(c->pending.begin(), c->pending.begin() + done);
 }
 
+// reduce `r` to one host scalar (optionally sqrt) through the context's pinned scratch
+int host_scalar(nk_ctx* c, Red r, int sqrt_it, double* out) {
+    NK_TRY(finish_reduction(c, &r));
+    NK_TRY(launch_finalize(c, r, c->scal, sqrt_it));
+    NK_HIP(c, hipMemcpyAsync(c->hpin, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    NK_TRY(nk_sync(c));  // the sync, prof_drain, mb_check
+    *out = c->hpin[0];
+    return NK_OK;
+}
+
 }  // namespace nk
 
 using namespace nk;
@@ -332,12 +342,7 @@ int nk_residual_norm(nk_ctx* c, const nk_problem* p, double* res, const double* 
     StencilIn in{p, MODE_RES, EPI_SUMSQ, res, u, nullptr, nullptr, nullptr, 0.0};
     Red r{};
     NK_TRY(launch_stencil(c, in, &r));
-    NK_TRY(finish_reduction(c, &r));
-    NK_TRY(launch_finalize(c, r, c->scal, 1));
-    NK_HIP(c, hipMemcpyAsync(c->hpin, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    NK_TRY(nk_sync(c));
-    *n_res = c->hpin[0];
-    return NK_OK;
+    return host_scalar(c, r, 1, n_res);
 }
 
 int nk_jv(nk_ctx* c, const nk_problem* p, double* out, const double* u, const double* v, const double* F0, int32_t mode,
@@ -409,27 +414,18 @@ int nk_jtv(nk_ctx* c, const nk_problem* p, double* out, const double* u, const d
 }
 
 // ---------------------------------------------------------------- Krylov vector primitives
-static int scalar_result(nk_ctx* c, Red r, int sqrt_it, double* out) {
-    NK_TRY(finish_reduction(c, &r));
-    NK_TRY(launch_finalize(c, r, c->scal, sqrt_it));
-    NK_HIP(c, hipMemcpyAsync(c->hpin, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    NK_TRY(nk_sync(c));
-    *out = c->hpin[0];
-    return NK_OK;
-}
-
 int nk_dot(nk_ctx* c, int64_t n, const double* x, const double* y, double* out) {
     if (!c || !out || n < 0) return NK_E_ARG;
     Red r{};
     NK_TRY(launch_dot(c, n, x, y, &r));
-    return scalar_result(c, r, 0, out);
+    return host_scalar(c, r, 0, out);
 }
 
 int nk_norm(nk_ctx* c, int64_t n, const double* x, double* out) {
     if (!c || !out || n < 0) return NK_E_ARG;
     Red r{};
     NK_TRY(launch_sumsq(c, n, x, &r));
-    return scalar_result(c, r, 1, out);
+    return host_scalar(c, r, 1, out);
 }
 
 int nk_scal(nk_ctx* c, int64_t n, double s, double* x) { return c ? launch_scal(c, n, s, x) : NK_E_ARG; }
@@ -438,7 +434,7 @@ int nk_axpy_norm(nk_ctx* c, int64_t n, double s, const double* x, double* y, dou
     if (!c || !ynorm || n < 0) return NK_E_ARG;
     Red r{};
     NK_TRY(launch_axpy_sumsq(c, n, s, x, y, &r));
-    return scalar_result(c, r, 1, ynorm);
+    return host_scalar(c, r, 1, ynorm);
 }
 int nk_axpby(nk_ctx* c, int64_t n, double s, const double* x, double t, double* y) {
     return c ? launch_axpby(c, n, s, x, t, y) : NK_E_ARG;

@@ -290,6 +290,7 @@ int wide_blocks(int64_t n);                  // grid of the streaming kernels wh
 int launch_dot(nk_ctx* c, int64_t n, const double* x, const double* y, Red* red);
 int launch_sumsq(nk_ctx* c, int64_t n, const double* x, Red* red);
 int launch_finalize(nk_ctx* c, Red r, double* dst, int sqrt_it, double* mirror = nullptr);  // dst[0] = sum (or sqrt(sum))
+int host_scalar(nk_ctx* c, Red r, int sqrt_it, double* out);  // r to one host scalar: finalise, copy, nk_sync (nk_core.cpp)
 int launch_axpy(nk_ctx* c, int64_t n, double s, const double* x, double* y);
 int launch_axpy_sumsq(nk_ctx* c, int64_t n, double s, const double* x, double* y, Red* red);  // + ||y||^2 partials
 int launch_axpby(nk_ctx* c, int64_t n, double s, const double* x, double t, double* y);

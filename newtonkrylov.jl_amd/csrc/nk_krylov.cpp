@@ -15,7 +15,7 @@
 //  * the per-cycle kfill!(V[i], 0) of Krylov.jl is dropped: every V[i] read in a cycle is
 //    overwritten first, so the zeroing is dead work (no observable difference).
 // The Givens rotations, the least-squares back-substitution and all stopping tests run on the
-// host on the same scalars, in the same order as Krylov.jl.
+// host on the same scalars, in the same order as Krylov.jl: nk_lsq.hpp, which needs no device.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "nk_internal.hpp"
+#include "nk_lsq.hpp"
 
 struct nk_workspace {
     nk_ctx* c = nullptr;
@@ -114,9 +115,6 @@ int ws_zbasis(nk_workspace* ws, int need) {
     return NK_OK;
 }
 
-
-inline double sgn(double x) { return (double)((x > 0) - (x < 0)); }
-
 // NK_MGS_RESIDENT=0 (operational) runs one k_mgs_pass launch per MGS pass instead
 // of the resident sweep, which needs every CU of the device at once: for a GPU shared with unrelated
 // work.  kbench knobs: NK_MGS_ALT=1 alternates the sweep direction of consecutive MGS passes (see
@@ -126,44 +124,47 @@ const int mgs_alt = NK_TUNE("NK_MGS_ALT", 0);
 const int mgs_resident = env_cfg("NK_MGS_RESIDENT", 1);
 const int mgs_fused_jv = NK_TUNE("NK_RES_JV", 0);
 
-// Krylov.jl sym_givens (real case)
-void sym_givens(double a, double b, double* c, double* s, double* rho) {
-    if (b == 0.0) {
-        *c = (a == 0.0) ? 1.0 : sgn(a);
-        *s = 0.0;
-        *rho = std::fabs(a);
-    } else if (a == 0.0) {
-        *c = 0.0;
-        *s = sgn(b);
-        *rho = std::fabs(b);
-    } else if (std::fabs(b) > std::fabs(a)) {
-        const double t = a / b;
-        *s = sgn(b) / std::sqrt(1.0 + t * t);
-        *c = *s * t;
-        *rho = b / *s;
-    } else {
-        const double t = b / a;
-        *c = sgn(a) / std::sqrt(1.0 + t * t);
-        *s = *c * t;
-        *rho = a / *c;
+// the residual history a caller asked for: every value counts, the first `cap` are kept
+struct Hist {
+    double* v;
+    int64_t cap;
+    int64_t n;
+    void push(double r) {
+        if (v && n < cap) v[n] = r;
+        ++n;
     }
-}
+    void close(int64_t* len) const {
+        if (len) *len = n;
+    }
+};
 
-// reduce `r` to one host scalar (optionally sqrt) through the context's pinned scratch
-int host_scalar(nk_ctx* c, Red r, int sqrt_it, double* out) {
-    NK_TRY(finish_reduction(c, &r));
-    NK_TRY(launch_finalize(c, r, c->scal, sqrt_it));
-    NK_HIP(c, hipMemcpyAsync(c->hpin, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    NK_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->prof) prof_drain(c, false);
-    NK_TRY(mb_check(c));
-    *out = c->hpin[0];
+// a solver's exit.  status: 1 solved, 2 tired, 3 breakdown, 4 zero curvature
+int finish(nk_krylov_stats* st, int64_t niter, bool solved, bool inconsistent, bool breakdown, int status) {
+    st->niter = niter;
+    st->solved = solved;
+    st->inconsistent = inconsistent;
+    st->breakdown = breakdown;
+    st->status = status;
+    return NK_OK;
+}
+// b = 0 (<r, M r> = 0): x = 0 solves it, no iteration
+int finish_at_zero(nk_krylov_stats* st) { return finish(st, 0, true, false, false, 1); }
+
+// the preconditioner a solve applies: null for none (Krylov.jl's I)
+const nk_precond* active(const nk_precond* P) { return (P && P->kind != NK_PRECOND_NONE) ? P : nullptr; }
+
+// *mg = the hierarchy of a multigrid preconditioner (null: P is none, or of another kind)
+int mg_of(nk_ctx* c, const nk_precond* P, nk_mg** mg) {
+    *mg = nullptr;
+    if (!P || P->kind != NK_PRECOND_MG) return NK_OK;
+    if (!P->data) return fail(c, NK_E_ARG, "multigrid preconditioner without its hierarchy (nk_mg_create)");
+    *mg = static_cast<nk_mg*>(P->data);
     return NK_OK;
 }
 
 struct Op;
 int gmres(nk_workspace* ws, const nk_problem* p, Op& A, const double* b, const nk_krylov_opts* o, nk_krylov_stats* st,
-          double* hist, int64_t hist_cap, int64_t* hist_len);
+          Hist& hist);
 
 struct Op {
     nk_ctx* c;
@@ -236,12 +237,14 @@ int apply_precond(nk_ctx* c, const nk_problem* p, const nk_precond* N, Op& A, in
         io.jv_mode = A.mode;
         io.atol = io.rtol = std::sqrt(DBL_EPSILON);
         nk_krylov_stats is{};
-        NK_TRY(gmres(N->inner, p, A, v, &io, &is, nullptr, 0, nullptr));
+        Hist none{nullptr, 0, 0};
+        NK_TRY(gmres(N->inner, p, A, v, &io, &is, none));
         NK_TRY(launch_copy(c, n, z, N->inner->x));
         if (need_norm) NK_TRY(launch_sumsq(c, n, z, &rz));
     } else if (N->kind == NK_PRECOND_MG) {
-        if (!N->data) return fail(c, NK_E_ARG, "multigrid preconditioner without its hierarchy (nk_mg_create)");
-        NK_TRY(nk_mg_apply(static_cast<nk_mg*>(N->data), z, v));
+        nk_mg* mg = nullptr;
+        NK_TRY(mg_of(c, N, &mg));
+        NK_TRY(nk_mg_apply(mg, z, v));
         if (need_norm) NK_TRY(launch_sumsq(c, n, z, &rz));
     } else {
         return fail(c, NK_E_ARG, "unknown preconditioner kind");
@@ -250,111 +253,69 @@ int apply_precond(nk_ctx* c, const nk_problem* p, const nk_precond* N, Op& A, in
     return NK_OK;
 }
 
-#define PUSH_HIST(v)                                   \
-    do {                                               \
-        if (hist && nh < hist_cap) hist[nh] = (v);     \
-        ++nh;                                          \
-    } while (0)
-
-int gmres(nk_workspace* ws, const nk_problem* p, Op& A, const double* b, const nk_krylov_opts* o, nk_krylov_stats* st,
-          double* hist, int64_t hist_cap, int64_t* hist_len) {
-    nk_ctx* c = ws->c;
-    const int64_t n = ws->n;
-    const int mem = ws->mem;
-    const int restart = o->restart, reorth = o->reorthogonalization;
-    int64_t itmax = o->itmax;
-    int64_t nh = 0;
-    double* x = ws->x;
-    double* W[2] = {ws->w, ws->w2};  // q_k lives in W[k & 1]
-
-    // host Krylov state (same layout as Krylov.jl: R column-packed)
-    int hcap = mem;
-    std::vector<double> cs(hcap), sn(hcap), z(hcap + 1), R((size_t)hcap * (hcap + 1) / 2);
-
-    NK_TRY(ws_basis(ws, mem));
-    NK_TRY(ws_scalars(ws, mem + 1));
-    // left preconditioner M (ldiv = false): r0 = M (b - A x), q = M A (N V_k); beta and the stopping
-    // test measure the preconditioned residual (Krylov.jl 0.10 gmres!, SURVEY.md Appendix A)
-    const nk_precond* Mp = (o->M && o->M->kind != NK_PRECOND_NONE) ? o->M : nullptr;
-    if (Mp) {
-        NK_TRY(ws_vec(ws, &ws->mr));
-        NK_TRY(ws_vec(ws, &ws->mw));
-    }
-    // x .= 0 ; r0 = b - A*0 = b.  x is only materialised when no cycle runs: the first cycle's
-    // update writes x = Σ y_i V_i directly (bit-identical to 0 + Σ y_i V_i), saving a pass over x.
-    Red rb{};
-    double beta = o->b_norm;  // the caller may know ||b|| already (Newton: b = F(u), ||F(u)|| just computed)
-    const double* r0 = b;
-    if (Mp) {  // r0 = M b, beta = ||M b||
-        NK_TRY(apply_precond(c, p, Mp, A, n, ws->mr, b, true, &beta));
-        r0 = ws->mr;
-    } else if (!(beta > 0.0)) {
-        NK_TRY(launch_sumsq(c, n, b, &rb));
-        NK_TRY(host_scalar(c, rb, 1, &beta));
-    }
-    double rNorm = beta;
-    PUSH_HIST(rNorm);
-    const double eps_ = o->atol + o->rtol * rNorm;
-    st->inconsistent = 0;
-    st->breakdown = 0;
-    if (beta == 0.0) {
-        NK_TRY(launch_fill(c, n, x, 0.0));
-        st->niter = 0;
-        st->solved = 1;
-        st->status = 1;
-        if (hist_len) *hist_len = nh;
-        return NK_OK;
-    }
-    if (itmax == 0) itmax = 2 * n;
-    const double btol = std::pow(DBL_EPSILON, 0.75);
-
-    // Issue Arnoldi step k (kernels + async copy of its Hessenberg column) without waiting.
-    // Step 1 applies J to the materialised V_1; step k >= 2 applies J to q_{k-1} / h_{k,k-1},
-    // reading h from the device and storing V_k on the way (fused kdivcopy!).
-    auto slot_dev = [&](int k) { return ws->hdev + (size_t)(k & 1) * (2 * ws->cap + 2); };
-    auto slot_pin = [&](int k) { return ws->hpin + (size_t)(k & 1) * (2 * ws->cap + 2); };
-    auto slot_pin_dev = [&](int k) { return ws->hpin_dev + (size_t)(k & 1) * (2 * ws->cap + 2); };
-    auto npasses_of = [&](int k) { return reorth ? 2 * k : k; };
-    const double* v1_src = r0;  // r0 of the current cycle; step 1 applies J to r0 / rNorm and stores V_1
-    double v1norm = 1.0;        // ||V_1|| = beta / rNorm
+// One GMRES solve's Arnoldi process on the device: issues step k (its kernels and the mirror of its
+// Hessenberg column into pinned memory) without waiting, and applies the cycle's y to x.
+// Step 1 applies J to r0 / rNorm and stores V_1; step k >= 2 applies J to q_{k-1} / h_{k,k-1},
+// reading h from the device and storing V_k on the way (fused kdivcopy!).
+struct Arnoldi {
+    nk_workspace* ws;
+    const nk_problem* p;
+    Op& A;
+    const nk_krylov_opts* o;
+    nk_ctx* c;
+    const int64_t n;
+    double* W[2];  // q_k lives in W[k & 1]
     // right preconditioner, without the one-step-ahead issue (the FD step size needs ||N V_k|| on
     // the host): fgmres! stores Z_k = N V_k and updates x += Z y; gmres! applies N to p = N V_k
     // only for the product and updates x += N (V y) (Krylov.jl 0.10 gmres! / fgmres!)
-    const nk_precond* N = (o->N && o->N->kind != NK_PRECOND_NONE) ? o->N : nullptr;
-    const bool flex = N && ws->algo == NK_ALGO_FGMRES;
-    const bool spec = N == nullptr && Mp == nullptr;
+    const nk_precond* N;
+    // left preconditioner M (ldiv = false): r0 = M (b - A x), q = M A (N V_k); beta and the stopping
+    // test measure the preconditioned residual (Krylov.jl 0.10 gmres!, SURVEY.md Appendix A)
+    const nk_precond* M;
+    const bool flex, spec;
+    const double* v1_src = nullptr;  // r0 of the current cycle; step 1 applies J to r0 / rNorm and stores V_1
+    double v1norm = 1.0;             // ||V_1|| = beta / rNorm
     // vready[k]: step k's resident sweep stored V_{k+1} itself, so step k+1's Jv reads it as is
-    std::vector<char> vready(mem + 2, 0);
-    auto issue = [&](int k) -> int {
-        NK_TRY(ws_basis(ws, k));
-        NK_TRY(ws_scalars(ws, k + 1));
-        const int np = npasses_of(k);
-        double* col = slot_dev(k);
-        double* colh = slot_pin_dev(k);  // the kernels mirror every entry into pinned host memory
+    std::vector<char> vready;
+
+    Arnoldi(nk_workspace* ws_, const nk_problem* p_, Op& A_, const nk_krylov_opts* o_)
+        : ws(ws_), p(p_), A(A_), o(o_), c(ws_->c), n(ws_->n), W{ws_->w, ws_->w2}, N(active(o_->N)), M(active(o_->M)),
+          flex(N && ws_->algo == NK_ALGO_FGMRES), spec(!N && !M), vready(ws_->mem + 2, 0) {}
+
+    size_t slot(int k) const { return (size_t)(k & 1) * (2 * ws->cap + 2); }
+    double* slot_dev(int k) const { return ws->hdev + slot(k); }
+    const double* slot_pin(int k) const { return ws->hpin + slot(k); }
+    double* slot_pin_dev(int k) const { return ws->hpin_dev + slot(k); }  // the kernels mirror every entry here
+    int npasses(int k) const { return o->reorthogonalization ? 2 * k : k; }
+    // what step k's Jv divides by and applies J to: h_{k,k-1} and q_{k-1} (step 1: rNorm and r0)
+    const double* hprev(int k) const { return k > 1 ? slot_dev(k - 1) + npasses(k - 1) : ws->bdev; }
+    const double* qprev(int k) const { return k > 1 ? W[(k - 1) & 1] : v1_src; }
+
+    // (c) kbench only (NK_RES_JV=1): 2D Bratu, FD Jv, V_k stored by the previous resident sweep: Jv + MGS
+    // sweep in ONE launch (q = J V_k is computed into the registers that hold it through the sweep).
+    // Returns 1 with nothing enqueued where that does not apply.
+    int sweep_with_jv(int k) {
+        if (!(mgs_fused_jv && spec && k >= 2 && vready[k - 1] && mgs_resident && A.mode == NK_JV_FD &&
+              p->kind == NK_BRATU2D))
+            return 1;
+        NK_TRY(ws_basis(ws, k + 1));
+        double* vnext = ws->V[k];
+        const ResJv jin{A.u, ws->V[k - 1], A.F0, ws->V[0], A.fd_eps(1.0), p->lambda, p->hx * p->hx, p->hy * p->hy, p->nx};
+        NK_TRY(halo_exchange(c, p, ws->V[k - 1]));
+        const int rc = launch_mgs_sweep(c, n, W[k & 1], ws->V.data(), k, npasses(k), Red{}, slot_dev(k), slot_pin_dev(k),
+                                        -1, &vnext, &jin);
+        if (rc != NK_OK) return rc;
+        ++A.n_matvec;
+        vready[k] = vnext != nullptr;
+        NK_HIP(c, hipEventRecord(ws->col_ready[k & 1], c->stream));
+        return NK_OK;
+    }
+
+    // (a) q = (M) J (N) V_k into W[k & 1], with the partials of <V_1, q> in *red
+    int matvec(int k, Red* red) {
         double* q = W[k & 1];
-        Red red{};
-        const double* hprev = k > 1 ? slot_dev(k - 1) + npasses_of(k - 1) : ws->bdev;
-        const double* qprev = k > 1 ? W[(k - 1) & 1] : v1_src;
-        if ((int)vready.size() < k + 2) vready.resize(k + 2, 0);
-        // 2D Bratu, FD Jv, V_k stored by the previous resident sweep: Jv + MGS sweep in ONE launch
-        // (q = J V_k is computed into the registers that hold it through the sweep)
-        if (mgs_fused_jv && spec && k >= 2 && vready[k - 1] && mgs_resident && A.mode == NK_JV_FD &&
-            p->kind == NK_BRATU2D) {
-            NK_TRY(ws_basis(ws, k + 1));
-            double* vnext = ws->V[k];
-            const ResJv jin{A.u, ws->V[k - 1], A.F0, ws->V[0], A.fd_eps(1.0), p->lambda, p->hx * p->hx, p->hy * p->hy, p->nx};
-            NK_TRY(halo_exchange(c, p, ws->V[k - 1]));
-            const int rc = launch_mgs_sweep(c, n, q, ws->V.data(), k, np, Red{}, col, colh, -1, &vnext, &jin);
-            if (rc != NK_OK && rc != 1) return rc;
-            if (rc == NK_OK) {
-                ++A.n_matvec;
-                vready[k] = vnext != nullptr;
-                NK_HIP(c, hipEventRecord(ws->col_ready[k & 1], c->stream));
-                return NK_OK;
-            }
-        }
-        if (N || Mp) {  // V_k = q_{k-1} / h (r0 / beta), Z_k = N V_k, q = M J Z_k, <V_1, q>
-            NK_TRY(launch_fd_point(c, n, nullptr, nullptr, qprev, hprev, 0.0, ws->V[k - 1]));
+        if (N || M) {  // V_k = q_{k-1} / h (r0 / beta), Z_k = N V_k, q = M J Z_k, <V_1, q>
+            NK_TRY(launch_fd_point(c, n, nullptr, nullptr, qprev(k), hprev(k), 0.0, ws->V[k - 1]));
             const double* zk = ws->V[k - 1];
             double znorm = k == 1 ? v1norm : 1.0;
             if (N) {
@@ -363,24 +324,25 @@ int gmres(nk_workspace* ws, const nk_problem* p, Op& A, const double* b, const n
                 NK_TRY(apply_precond(c, p, N, A, n, z, ws->V[k - 1], A.mode == NK_JV_FD, &znorm));
                 zk = z;
             }
-            if (Mp) {  // w = J Z_k; q = M w
-                NK_TRY(A.apply(ws->mw, zk, znorm, EPI_NONE, nullptr, nullptr));
-                double unused = 0.0;
-                NK_TRY(apply_precond(c, p, Mp, A, n, q, ws->mw, false, &unused));
-                NK_TRY(launch_dot(c, n, ws->V[0], q, &red));
-            } else {
-                NK_TRY(A.apply(q, zk, znorm, EPI_DOT, ws->V[0], &red));
-            }
-        } else if (k == 1) {  // fused kdivcopy!(V_1, r0, rNorm) + mul! + <V_1, Jv> (the dot partner is V_1 itself)
-            // ||V_1|| = beta / rNorm: 1 on the first cycle, |r0| / |zeta| after a restart (the FD step's ||v||)
-            NK_TRY(A.apply(q, v1_src, v1norm, EPI_DOT, nullptr, &red, ws->bdev, ws->V[0]));
-        } else if (vready[k - 1]) {  // V_k is in place: mul! + <V_1, Jv> only
-            NK_TRY(A.apply(q, ws->V[k - 1], 1.0, EPI_DOT, ws->V[0], &red));
-        } else {
-            NK_TRY(A.apply(q, qprev, 1.0, EPI_DOT, ws->V[0], &red, hprev, ws->V[k - 1]));
+            if (!M) return A.apply(q, zk, znorm, EPI_DOT, ws->V[0], red);
+            NK_TRY(A.apply(ws->mw, zk, znorm, EPI_NONE, nullptr, nullptr));  // w = J Z_k; q = M w
+            double unused = 0.0;
+            NK_TRY(apply_precond(c, p, M, A, n, q, ws->mw, false, &unused));
+            return launch_dot(c, n, ws->V[0], q, red);
         }
-        vready[k] = 0;
-        // the whole sweep in one launch with q resident on chip, else one launch per pass
+        // fused kdivcopy!(V_1, r0, rNorm) + mul! + <V_1, Jv> (the dot partner is V_1 itself).
+        // ||V_1|| = beta / rNorm: 1 on the first cycle, |r0| / |zeta| after a restart (the FD step's ||v||)
+        if (k == 1) return A.apply(q, v1_src, v1norm, EPI_DOT, nullptr, red, ws->bdev, ws->V[0]);
+        // V_k is in place: mul! + <V_1, Jv> only
+        if (vready[k - 1]) return A.apply(q, ws->V[k - 1], 1.0, EPI_DOT, ws->V[0], red);
+        return A.apply(q, qprev(k), 1.0, EPI_DOT, ws->V[0], red, hprev(k), ws->V[k - 1]);
+    }
+
+    // (b) the MGS passes of step k over q, h_{k+1,k} = ||q||, and the column's event: the whole sweep
+    // in one launch with q resident on chip, else one launch per pass
+    int orthogonalize(int k, Red red) {
+        const int np = npasses(k);
+        double *q = W[k & 1], *col = slot_dev(k), *colh = slot_pin_dev(k);
         int rc = 1;
         if (mgs_resident) {
             NK_TRY(finish_reduction(c, &red));
@@ -407,152 +369,174 @@ int gmres(nk_workspace* ws, const nk_problem* p, Op& A, const double* b, const n
         }
         NK_HIP(c, hipEventRecord(ws->col_ready[k & 1], c->stream));  // column complete in pinned memory
         return NK_OK;
-    };
+    }
 
-    int npass = 0;
-    int64_t iter = 0, inner_iter = 0;
-    int64_t inner_itmax = itmax;
-    bool breakdown = false, inconsistent = false;
-    bool solved = rNorm <= eps_;
-    bool tired = iter >= itmax;
-    double xnorm = 0.0;  // ||x|| for the FD restart residual (from the fused x update)
-    while (!(solved || tired || breakdown)) {
-        int64_t nr = 0;
-        std::fill(cs.begin(), cs.end(), 0.0);
-        std::fill(sn.begin(), sn.end(), 0.0);
-        std::fill(z.begin(), z.end(), 0.0);
-        std::fill(R.begin(), R.end(), 0.0);
-        const double* src = r0;
-        if (restart && npass >= 1) {
-            Red rr{};
-            NK_TRY(A.apply(W[0], x, xnorm, EPI_RESID, b, &rr));  // w = b - A x, fused ||w||^2 partials
-            NK_TRY(host_scalar(c, rr, 1, &beta));
-            src = W[0];
-            if (Mp) {  // r0 = M w, beta = ||r0||
-                NK_TRY(apply_precond(c, p, Mp, A, n, ws->mr, W[0], true, &beta));
-                src = ws->mr;
-            }
+    // Issue Arnoldi step k.  It writes only V_k (V_{k+1} too where the sweep stores it), q_k = W[k & 1],
+    // slot k & 1 of the column buffers and vready[k]: the speculation below rests on that.
+    int issue(int k) {
+        NK_TRY(ws_basis(ws, k));
+        NK_TRY(ws_scalars(ws, k + 1));
+        if ((int)vready.size() < k + 2) vready.resize(k + 2, 0);
+        const int rc = sweep_with_jv(k);
+        if (rc != 1) return rc;
+        Red red{};
+        NK_TRY(matvec(k, &red));
+        vready[k] = 0;
+        return orthogonalize(k, red);
+    }
+
+    // Before the host waits for step k's column.  Unpreconditioned, step k is in flight already and
+    // step k+1 is issued ahead of the column it depends on (its Jv divides by h_{k+1,k} on the device),
+    // unless the cycle certainly ends at k.  If the column then ends the cycle, step k+1 is discarded:
+    // it wrote only V_{k+1}, q_{k+1}, slot (k+1) & 1 and vready[k+1], none of which is read when the
+    // cycle stops at k (the x update reads V_1 .. V_k and y), and gmres() takes its mul!(J) back out of
+    // n_matvec.  Preconditioned (the FD step needs a norm on the host), step k is issued when it is needed.
+    int issue_ahead(int k, bool last) {
+        if (!spec && k > 1) NK_TRY(issue(k));
+        if (spec && !last) NK_TRY(issue(k + 1));
+        return NK_OK;
+    }
+
+    // a restarted cycle's r0 = (M) (b - A x) in *src, its norm in *beta
+    int restart_residual(const double* b, double xnorm, double* beta, const double** src) {
+        Red rr{};
+        NK_TRY(A.apply(W[0], ws->x, xnorm, EPI_RESID, b, &rr));  // w = b - A x, fused ||w||^2 partials
+        NK_TRY(host_scalar(c, rr, 1, beta));
+        *src = W[0];
+        if (M) {  // r0 = M w, beta = ||r0||
+            NK_TRY(apply_precond(c, p, M, A, n, ws->mr, W[0], true, beta));
+            *src = ws->mr;
         }
-        Range cycle_range("gmres_cycle");
-        z[0] = beta;
-        // kdivcopy!(n, V[1], r0, rNorm) inside step 1's Jv: Krylov.jl divides by rNorm, which is beta on
-        // the first pass and, after a restart, the previous cycle's estimate |zeta| (z[1] = beta regardless)
-        NK_TRY(launch_fill(c, 1, ws->bdev, rNorm));
-        v1_src = src;
-        v1norm = beta / rNorm;
-        npass++;
-        inner_iter = 0;
-        bool inner_tired = false;
-        NK_TRY(issue(1));
-        while (!(solved || inner_tired || breakdown)) {
-            inner_iter++;
-            const int k = (int)inner_iter;
-            if (k + 1 > hcap) {  // unrestarted GMRES grows beyond `memory`
-                int nc = hcap * 2;
-                cs.resize(nc, 0.0);
-                sn.resize(nc, 0.0);
-                z.resize(nc + 1, 0.0);
-                R.resize((size_t)nc * (nc + 1) / 2, 0.0);
-                hcap = nc;
-            }
-            // speculate: step k+1 unless the cycle certainly ends at k (its kernels only write
-            // V_{k+1}, q_{k+1} and slot (k+1)&1, none of which is read if the cycle stops here)
-            const bool last = restart ? (inner_iter >= std::min<int64_t>(mem, inner_itmax)) : (inner_iter >= inner_itmax);
-            if (!spec && k > 1) NK_TRY(issue(k));  // preconditioned: step k is issued when it is needed
-            if (spec && !last) NK_TRY(issue(k + 1));
-            NK_HIP(c, hipEventSynchronize(ws->col_ready[k & 1]));
-            NK_TRY(mb_check(c));
-            if (c->prof) prof_drain(c, false);
-            const double* hcol = slot_pin(k);
-            const int np = npasses_of(k);
-            for (int i = 0; i < k; ++i) R[nr + i] = hcol[i];
-            if (reorth)
-                for (int i = 0; i < k; ++i) R[nr + i] += hcol[k + i];
-            const double Hbis = hcol[np];
-            for (int i = 1; i <= k - 1; ++i) {
-                const double Rtmp = cs[i - 1] * R[nr + i - 1] + sn[i - 1] * R[nr + i];
-                R[nr + i] = sn[i - 1] * R[nr + i - 1] - cs[i - 1] * R[nr + i];
-                R[nr + i - 1] = Rtmp;
-            }
-            sym_givens(R[nr + k - 1], Hbis, &cs[k - 1], &sn[k - 1], &R[nr + k - 1]);
-            const double zeta = sn[k - 1] * z[k - 1];
-            z[k - 1] = cs[k - 1] * z[k - 1];
-            rNorm = std::fabs(zeta);
-            PUSH_HIST(rNorm);
-            nr += k;
-            const bool mach = (rNorm + 1.0 <= 1.0);
-            solved = (rNorm <= eps_) || mach;
-            breakdown = Hbis <= btol;
-            inner_tired = last;
-            if (!(solved || inner_tired || breakdown)) z[k] = zeta;  // V_{k+1} = q/h was stored by step k+1
-            else if (spec && !last) A.n_matvec -= 1;  // the speculative step k+1 is discarded: not a mul!(J) of the solve
-        }
-        // back substitution R y = z (Krylov.jl, y stored in z)
-        const int kk = (int)inner_iter;
-        for (int i = kk; i >= 1; --i) {
-            int64_t pos = nr + i - kk;
-            for (int j = kk; j >= i + 1; --j) {
-                z[i - 1] = z[i - 1] - R[pos - 1] * z[j - 1];
-                pos = pos - j + 1;
-            }
-            if (std::fabs(R[pos - 1]) <= btol) {
-                z[i - 1] = 0.0;
-                inconsistent = true;
-            } else {
-                z[i - 1] = z[i - 1] / R[pos - 1];
-            }
-        }
+        return NK_OK;
+    }
+
+    // The cycle's x update from its kk coefficients y: x = V y (x += from the second restarted cycle on,
+    // `accumulate`), Z y for fgmres!, x (+)= N (V y) for gmres! with N.  The final cycle fuses the Newton
+    // update u .-= x and leaves ||u|| in st->u_norm; a restarted FD solve that goes on needs ||x|| (*xnorm).
+    int update_x(const double* y, int kk, bool accumulate, bool final_cycle, nk_krylov_stats* st, double* xnorm) {
         NK_TRY(ws_scalars(ws, kk + 1));
-        for (int i = 0; i < kk; ++i) ws->ypin[i] = z[i];
+        for (int i = 0; i < kk; ++i) ws->ypin[i] = y[i];
         NK_HIP(c, hipMemcpyAsync(ws->ydev, ws->ypin, sizeof(double) * kk, hipMemcpyHostToDevice, c->stream));
-        iter += inner_iter;
-        inner_itmax = itmax - iter;
-        tired = iter >= itmax;
-        const bool final_cycle = solved || tired || breakdown;
-        const bool need_xnorm = restart && A.mode == NK_JV_FD && !final_cycle;
+        const bool need_xnorm = o->restart && A.mode == NK_JV_FD && !final_cycle;
         double* uu = final_cycle ? o->u_update : nullptr;  // fused Newton update u .-= x
+        double* x = ws->x;
         Red xr{};
         if (N && !flex) {  // gmres!: xr = V y; p = xr; xr = N p; x += xr (restart) -- x = xr otherwise
             uu = nullptr;  // not fused: nk_krylov_solve applies u .-= x afterwards
             NK_TRY(launch_update_x(c, n, W[0], ws->xr, ws->V.data(), kk, ws->ydev, 0, nullptr, nullptr));
             double dummy = 0.0;
             NK_TRY(apply_precond(c, p, N, A, n, ws->Z[0], W[0], false, &dummy));
-            if (restart && npass > 1) NK_TRY(launch_axpy(c, n, 1.0, ws->Z[0], x));
+            if (accumulate) NK_TRY(launch_axpy(c, n, 1.0, ws->Z[0], x));
             else NK_TRY(launch_copy(c, n, x, ws->Z[0]));
             if (need_xnorm) NK_TRY(launch_sumsq(c, n, x, &xr));
         } else {
-            NK_TRY(launch_update_x(c, n, x, ws->xr, N ? ws->Z.data() : ws->V.data(), kk, ws->ydev, restart && npass > 1,
+            NK_TRY(launch_update_x(c, n, x, ws->xr, N ? ws->Z.data() : ws->V.data(), kk, ws->ydev, accumulate,
                                    (need_xnorm || uu) ? &xr : nullptr, uu));
         }
         if (uu) {
             NK_TRY(host_scalar(c, xr, 1, &st->u_norm));
             ws->u_fused = true;
+            return NK_OK;
         }
-        else if (need_xnorm) NK_TRY(host_scalar(c, xr, 1, &xnorm));
-        else {
-            NK_HIP(c, hipStreamSynchronize(c->stream));  // ypin may be rewritten next cycle
-        }
+        if (need_xnorm) return host_scalar(c, xr, 1, xnorm);
+        NK_HIP(c, hipStreamSynchronize(c->stream));  // ypin may be rewritten next cycle
+        return NK_OK;
     }
-    if (npass == 0) NK_TRY(launch_fill(c, n, x, 0.0));  // solved (or tired) before the first cycle
-    st->niter = iter;
-    st->solved = solved;
-    st->inconsistent = inconsistent;
-    st->breakdown = breakdown;
-    st->status = solved ? 1 : (tired ? 2 : (breakdown ? 3 : 0));
-    if (hist_len) *hist_len = nh;
-    return NK_OK;
-}
+};
 
-int cg(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk_krylov_stats* st, double* hist,
-       int64_t hist_cap, int64_t* hist_len) {
+int gmres(nk_workspace* ws, const nk_problem* p, Op& A, const double* b, const nk_krylov_opts* o, nk_krylov_stats* st,
+          Hist& hist) {
     nk_ctx* c = ws->c;
     const int64_t n = ws->n;
-    int64_t nh = 0;
+    const int mem = ws->mem;
+    const bool restart = o->restart != 0, reorth = o->reorthogonalization != 0;
+    NK_TRY(ws_basis(ws, mem));
+    NK_TRY(ws_scalars(ws, mem + 1));
+    Arnoldi S(ws, p, A, o);
+    if (S.M) {
+        NK_TRY(ws_vec(ws, &ws->mr));
+        NK_TRY(ws_vec(ws, &ws->mw));
+    }
+    // x .= 0 ; r0 = b - A*0 = b.  x is only materialised when no cycle runs: the first cycle's
+    // update writes x = Σ y_i V_i directly (bit-identical to 0 + Σ y_i V_i), saving a pass over x.
+    double beta = o->b_norm;  // the caller may know ||b|| already (Newton: b = F(u), ||F(u)|| just computed)
+    const double* r0 = b;
+    if (S.M) {  // r0 = M b, beta = ||M b||
+        NK_TRY(apply_precond(c, p, S.M, A, n, ws->mr, b, true, &beta));
+        r0 = ws->mr;
+    } else if (!(beta > 0.0)) {
+        Red rb{};
+        NK_TRY(launch_sumsq(c, n, b, &rb));
+        NK_TRY(host_scalar(c, rb, 1, &beta));
+    }
+    double rNorm = beta;
+    hist.push(rNorm);
+    const double eps_ = o->atol + o->rtol * rNorm;
+    if (beta == 0.0) {
+        NK_TRY(launch_fill(c, n, ws->x, 0.0));
+        return finish_at_zero(st);
+    }
+    const int64_t itmax = o->itmax == 0 ? 2 * n : o->itmax;
+    const double btol = gmres_btol();
+    GmresLsq lsq(mem);
+
+    int npass = 0;
+    int64_t iter = 0, inner_itmax = itmax;
+    bool breakdown = false, inconsistent = false;
+    bool solved = rNorm <= eps_;
+    bool tired = iter >= itmax;
+    double xnorm = 0.0;  // ||x|| for the FD restart residual (from the fused x update)
+    while (!(solved || tired || breakdown)) {
+        const double* src = r0;
+        if (restart && npass >= 1) NK_TRY(S.restart_residual(b, xnorm, &beta, &src));
+        Range cycle_range("gmres_cycle");
+        lsq.start(beta);
+        // kdivcopy!(n, V[1], r0, rNorm) inside step 1's Jv: Krylov.jl divides by rNorm, which is beta on
+        // the first pass and, after a restart, the previous cycle's estimate |zeta| (z[1] = beta regardless)
+        NK_TRY(launch_fill(c, 1, ws->bdev, rNorm));
+        S.v1_src = src;
+        S.v1norm = beta / rNorm;
+        npass++;
+        int64_t inner_iter = 0;
+        bool inner_tired = false;
+        NK_TRY(S.issue(1));
+        while (!(solved || inner_tired || breakdown)) {
+            inner_iter++;
+            const int k = (int)inner_iter;
+            const bool last = gmres_last(restart, inner_iter, mem, inner_itmax);
+            NK_TRY(S.issue_ahead(k, last));
+            NK_HIP(c, hipEventSynchronize(ws->col_ready[k & 1]));
+            NK_TRY(mb_check(c));
+            if (c->prof) prof_drain(c, false);
+            const GmresLsq::Col h = lsq.column(k, S.slot_pin(k), reorth);
+            rNorm = h.rNorm;
+            hist.push(rNorm);
+            solved = gmres_solved(rNorm, eps_);
+            breakdown = gmres_breakdown(h.Hbis, btol);
+            inner_tired = last;
+            if (!(solved || inner_tired || breakdown)) lsq.accept(k, h.zeta);  // V_{k+1} = q/h was stored by step k+1
+            else if (S.spec && !last) A.n_matvec -= 1;  // the speculative step k+1 is discarded: not a mul!(J) of the solve
+        }
+        const int kk = (int)inner_iter;
+        if (lsq.solve(kk, btol)) inconsistent = true;
+        iter += inner_iter;
+        inner_itmax = itmax - iter;
+        tired = iter >= itmax;
+        NK_TRY(S.update_x(lsq.y(), kk, restart && npass > 1, solved || tired || breakdown, st, &xnorm));
+    }
+    if (npass == 0) NK_TRY(launch_fill(c, n, ws->x, 0.0));  // solved (or tired) before the first cycle
+    return finish(st, iter, solved, inconsistent, breakdown, solved ? 1 : (tired ? 2 : (breakdown ? 3 : 0)));
+}
+
+int cg(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk_krylov_stats* st, Hist& hist) {
+    nk_ctx* c = ws->c;
+    const int64_t n = ws->n;
     double *x = ws->x, *r = ws->xr, *p = ws->p, *Ap = ws->w;
     // preconditioner M (Krylov.jl cg!: z = M r, gamma = <r, z>, p = z + beta p); M = I: z === r
-    const nk_precond* Mp = (o->M && o->M->kind != NK_PRECOND_NONE) ? o->M : nullptr;
+    const nk_precond* Mp = active(o->M);
     // M = a multigrid hierarchy (in SPD form, nk_krylov_solve checked): the cycle's last launch leaves <r, z> itself
-    nk_mg* Mg = (Mp && Mp->kind == NK_PRECOND_MG) ? static_cast<nk_mg*>(Mp->data) : nullptr;
+    nk_mg* Mg = nullptr;
+    NK_TRY(mg_of(c, Mp, &Mg));
     double* zr = r;
     if (Mp) {
         NK_TRY(ws_vec(ws, &ws->mr));
@@ -570,16 +554,8 @@ int cg(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk_kry
     double gamma = 0.0;
     NK_TRY(host_scalar(c, rg, 0, &gamma));
     double rNorm = std::sqrt(gamma);
-    PUSH_HIST(rNorm);
-    st->inconsistent = 0;
-    st->breakdown = 0;
-    if (gamma == 0.0) {
-        st->niter = 0;
-        st->solved = 1;
-        st->status = 1;
-        if (hist_len) *hist_len = nh;
-        return NK_OK;
-    }
+    hist.push(rNorm);
+    if (gamma == 0.0) return finish_at_zero(st);
     int64_t iter = 0, itmax = o->itmax == 0 ? 2 * n : o->itmax;
     double pNorm2 = gamma;
     const double eps_ = o->atol + o->rtol * rNorm;
@@ -616,7 +592,7 @@ int cg(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk_kry
         double gamma_next = 0.0;
         NK_TRY(host_scalar(c, rn, 0, &gamma_next));
         rNorm = std::sqrt(gamma_next);
-        PUSH_HIST(rNorm);
+        hist.push(rNorm);
         const bool mach = (rNorm + 1.0 <= 1.0);
         solved = (rNorm <= eps_) || mach;
         if (!solved) {
@@ -629,12 +605,7 @@ int cg(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk_kry
         tired = iter >= itmax;
     }
     NK_HIP(c, hipStreamSynchronize(c->stream));
-    st->niter = iter;
-    st->solved = solved;
-    st->inconsistent = inconsistent;
-    st->status = solved ? 1 : (tired ? 2 : (zero_curvature ? 4 : 0));
-    if (hist_len) *hist_len = nh;
-    return NK_OK;
+    return finish(st, iter, solved, inconsistent, false, solved ? 1 : (tired ? 2 : (zero_curvature ? 4 : 0)));
 }
 
 // kbench knob: NK_MINRES_BLAS1=1 assembles the Lanczos step from the BLAS-1 launches (axpy, axpy, sumsq / diagonal
@@ -647,14 +618,13 @@ const int minres_blas1 = NK_TUNE("NK_MINRES_BLAS1", 0);
 // to y / beta with beta on the device, stores v, emits <v, Jv>), k_minres_lanczos, M where it is not the diagonal,
 // k_minres_scalars, ONE host synchronisation (alpha and beta^2 arrive together), then k_minres_update with the
 // rotation's scalars by value.
-int minres(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk_krylov_stats* st, double* hist,
-           int64_t hist_cap, int64_t* hist_len) {
+int minres(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk_krylov_stats* st, Hist& hist) {
     nk_ctx* c = ws->c;
     const int64_t n = ws->n;
-    int64_t nh = 0;
     double *x = ws->x, *jv = ws->w, *r1 = ws->xr, *r2 = ws->mv[0], *v = ws->mv[1], *w1 = ws->mv[2], *w2 = ws->mv[3];
-    const nk_precond* Mp = (o->M && o->M->kind != NK_PRECOND_NONE) ? o->M : nullptr;
-    nk_mg* Mg = (Mp && Mp->kind == NK_PRECOND_MG) ? static_cast<nk_mg*>(Mp->data) : nullptr;
+    const nk_precond* Mp = active(o->M);
+    nk_mg* Mg = nullptr;
+    NK_TRY(mg_of(c, Mp, &Mg));
     const double* Md = (Mp && Mp->kind == NK_PRECOND_DIAG) ? Mp->diag : nullptr;
     if (Mp && Mp->kind == NK_PRECOND_DIAG && !Md) return fail(c, NK_E_ARG, "diagonal preconditioner without its diagonal");
     if (Mp) NK_TRY(ws_vec(ws, &ws->mr));
@@ -693,23 +663,15 @@ int minres(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk
     NK_TRY(precond(r2, &rb, &ry));
     NK_TRY(scalars(rb, ry, 1));
     double beta2 = hp[1], ynorm = std::sqrt(hp[2]);
-    st->inconsistent = 0;
-    st->breakdown = 0;
     bool breakdown = beta2 < 0.0;  // <r, M r> < 0: M is not positive definite
     const double beta1 = std::sqrt(beta2);
-    PUSH_HIST(beta1);
-    if (beta2 == 0.0 || breakdown) {
-        st->niter = 0;
-        st->solved = breakdown ? 0 : 1;
-        st->breakdown = breakdown;
-        st->status = breakdown ? 3 : 1;
-        if (hist_len) *hist_len = nh;
-        return NK_OK;
-    }
+    hist.push(beta1);
+    if (breakdown) return finish(st, 0, false, false, true, 3);
+    if (beta2 == 0.0) return finish_at_zero(st);
     int64_t iter = 0, itmax = o->itmax == 0 ? 2 * n : o->itmax;
-    double oldb = 0.0, beta = beta1, dbar = 0.0, eps = 0.0, phibar = beta1, cs = -1.0, sn = 0.0;
+    MinresRot rot(beta1);  // the rotation's scalars (nk_lsq.hpp)
     const double tol = o->atol + o->rtol * beta1;
-    bool solved = phibar <= tol, tired = iter >= itmax;
+    bool solved = rot.phibar <= tol, tired = iter >= itmax;
     while (!(solved || tired || breakdown)) {
         iter++;
         const int first = iter == 1;
@@ -717,15 +679,15 @@ int minres(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk
         const double* odev = sc + (iter + 2) % 3;
         Red ra{};
         // J (y / beta), v = y / beta stored, partials of <v, J v>
-        NK_TRY(A.apply(jv, y, Mp ? ynorm / beta : 1.0, EPI_DOT, nullptr, &ra, bdev, v));
+        NK_TRY(A.apply(jv, y, Mp ? ynorm / rot.beta : 1.0, EPI_DOT, nullptr, &ra, bdev, v));
         rb = Red{};
         ry = Red{};
         if (minres_blas1 && (!Mp || Md)) {
             double alpha = 0.0;
             NK_TRY(host_scalar(c, ra, 0, &alpha));
             hp[0] = alpha;
-            if (!first) NK_TRY(launch_axpy(c, n, -(beta / oldb), r1, jv));
-            NK_TRY(launch_axpy(c, n, -(alpha / beta), r2, jv));
+            if (!first) NK_TRY(launch_axpy(c, n, -(rot.beta / rot.oldb), r1, jv));
+            NK_TRY(launch_axpy(c, n, -(alpha / rot.beta), r2, jv));
             std::swap(jv, r1);  // t is where r1 is rotated from
             if (Md) {
                 NK_TRY(launch_diag_apply(c, n, y, Md, r1, need_yn ? &ry : nullptr));
@@ -751,32 +713,16 @@ int minres(nk_workspace* ws, Op& A, const double* b, const nk_krylov_opts* o, nk
             break;
         }
         ynorm = std::sqrt(hp[2]);
-        oldb = beta;
-        beta = std::sqrt(beta2);
-        const double oldeps = eps;
-        const double delta = cs * dbar + sn * alpha;
-        const double gbar = sn * dbar - cs * alpha;
-        eps = sn * beta;
-        dbar = -cs * beta;
-        const double gamma = std::fmax(std::sqrt(gbar * gbar + beta * beta), DBL_EPSILON);
-        cs = gbar / gamma;
-        sn = beta / gamma;
-        const double phi = cs * phibar;
-        phibar = sn * phibar;
+        const MinresRot::Step s = rot.step(alpha, beta2);
         // w = ((v - oldeps w1) - delta w2) / gamma over w1; x += phi w
-        NK_TRY(launch_minres_update(c, n, v, w1, w2, x, oldeps, delta, gamma, phi));
+        NK_TRY(launch_minres_update(c, n, v, w1, w2, x, s.oldeps, s.delta, s.gamma, s.phi));
         std::swap(w1, w2);  // w1 = w2; w2 = w
-        PUSH_HIST(phibar);
-        solved = phibar <= tol;
+        hist.push(rot.phibar);
+        solved = rot.phibar <= tol;
         tired = iter >= itmax;
     }
     NK_HIP(c, hipStreamSynchronize(c->stream));
-    st->niter = iter;
-    st->solved = solved;
-    st->breakdown = breakdown;
-    st->status = solved ? 1 : (breakdown ? 3 : (tired ? 2 : 0));
-    if (hist_len) *hist_len = nh;
-    return NK_OK;
+    return finish(st, iter, solved, false, breakdown, solved ? 1 : (breakdown ? 3 : (tired ? 2 : 0)));
 }
 
 }  // namespace
@@ -912,19 +858,21 @@ int nk_krylov_solve(nk_workspace* ws, const nk_problem* p, const double* u, cons
     }
     ws->u_fused = false;
     const bool sym = ws->algo == NK_ALGO_CG || ws->algo == NK_ALGO_MINRES;  // the short recurrences: M SPD, no N
-    if (sym && o->N && o->N->kind != NK_PRECOND_NONE)
+    if (sym && active(o->N))
         return fail(c, NK_E_ARG, ws->algo == NK_ALGO_CG ? "the device CG takes no right preconditioner (use GMRES / FGMRES)"
                                                         : "the device MINRES takes no right preconditioner (use GMRES / FGMRES)");
-    if (sym && o->M && o->M->kind == NK_PRECOND_MG) {
-        if (!o->M->data) return fail(c, NK_E_ARG, "multigrid preconditioner without its hierarchy (nk_mg_create)");
-        if (!mg_is_spd(static_cast<nk_mg*>(o->M->data)))
-            return fail(c, NK_E_ARG, "the multigrid V-cycle as CG's M is not supported in its default form: CG needs an SPD M "
-                                     "(nk_mg_set_spd, or use GMRES / FGMRES)");
-    }
+    nk_mg* Mg = nullptr;
+    if (sym) NK_TRY(mg_of(c, o->M, &Mg));
+    if (Mg && !mg_is_spd(Mg))
+        return fail(c, NK_E_ARG, "the multigrid V-cycle as CG's M is not supported in its default form: CG needs an SPD M "
+                                 "(nk_mg_set_spd, or use GMRES / FGMRES)");
     auto run = [&] {
-        return ws->algo == NK_ALGO_CG       ? cg(ws, A, b, o, st, hist, hist_cap, hist_len)
-               : ws->algo == NK_ALGO_MINRES ? minres(ws, A, b, o, st, hist, hist_cap, hist_len)
-                                            : gmres(ws, p, A, b, o, st, hist, hist_cap, hist_len);
+        Hist h{hist, hist_cap, 0};
+        const int rc = ws->algo == NK_ALGO_CG       ? cg(ws, A, b, o, st, h)
+                       : ws->algo == NK_ALGO_MINRES ? minres(ws, A, b, o, st, h)
+                                                    : gmres(ws, p, A, b, o, st, h);
+        if (rc == NK_OK) h.close(hist_len);
+        return rc;
     };
     int rc = run();
     if (rc != NK_OK && c->ilu_redo && !ws->u_fused && c->nranks == 1) {

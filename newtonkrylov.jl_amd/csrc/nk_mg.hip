@@ -957,12 +957,7 @@ int nk_mg_apply_dot(nk_mg* m, double* z, const double* v, double* vz) {
     nk_ctx* c = m->c;
     Red r{};
     NK_TRY(mg_apply_red(m, z, v, &r));
-    NK_TRY(finish_reduction(c, &r));
-    NK_TRY(launch_finalize(c, r, c->scal, 0));
-    NK_HIP(c, hipMemcpyAsync(c->hpin, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    NK_TRY(nk_sync(c));
-    *vz = c->hpin[0];
-    return NK_OK;
+    return host_scalar(c, r, 0, vz);
 }
 
 }  // extern "C"

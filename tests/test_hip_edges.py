@@ -84,6 +84,28 @@ def test_itmax_cap(ctx, algo):
     np.testing.assert_array_equal(x, xr)
 
 
+@pytest.mark.parametrize("reorth", [False, True])
+def test_unrestarted_gmres_grows_past_memory(ctx, reorth):
+    """memory = 5, no restart, 70 steps: the basis and the host least-squares arrays grow past `memory`, and past 64
+    vectors the device and pinned column buffers are reallocated while a column is in flight.  History, x and the
+    counts are the oracle's in device order, bit for bit."""
+    P = oc.bratu2d(48, 40)
+    u0 = oc.sin_ic(P)
+    J, res = setup(P, u0)
+    kw = dict(itmax=70, atol=0.0, rtol=0.0, restart=False, reorthogonalization=reorth)
+    ws = ah.krylov_workspace("gmres", ah.KrylovConstructor(res, memory=5))
+    x, st = solve(ws, J, res, **kw)
+    oc.set_devred(True)
+    try:
+        xr, so, hr = oc.krylov_solve(P, u0, res.to_numpy(), algo="gmres", jv="exact", memory=5, **kw)
+    finally:
+        oc.set_devred(False)
+    assert st.niter == so["niter"] == 70
+    assert st.n_matvec == so["n_matvec"]
+    np.testing.assert_array_equal(np.array(st.residuals), hr)
+    np.testing.assert_array_equal(x, xr)
+
+
 @pytest.mark.parametrize("nx,ny", [(3, 3), (5, 2), (4, 4)])
 def test_gmres_exhausts_krylov_space(ctx, nx, ny):
     """GMRES with memory > n and no tolerance: the Arnoldi process runs out of directions (h_{k+1,k}

@@ -63,9 +63,10 @@ GOOD = "solution good enough given atol and rtol"
 
 
 # ------------------------------------------------------------------------------------ the restatement
-def minres_ref(A, b, M=None, itmax=0, atol=0.0, rtol=0.0, dt=np.float64):
+def minres_ref(A, b, M=None, itmax=0, atol=0.0, rtol=0.0, dt=np.float64, trace=None):
     """The recurrence of DESIGN.md §11 in dtype dt.  A: a matrix or a callable on flat vectors; M: a callable (SPD) or
-    None.  Returns (x, history, niter, status) with status 1 solved, 2 itmax, 3 breakdown."""
+    None.  Returns (x, history, niter, status) with status 1 solved, 2 itmax, 3 breakdown.  `trace` (a list) receives
+    every completed step's rotation scalars (alpha, g = <r2, y>, oldeps, delta, gamma, phi)."""
     mul = A if callable(A) else (lambda q: A @ q)
     b = np.asarray(b, dtype=dt).reshape(-1)
     n = b.size
@@ -109,6 +110,8 @@ def minres_ref(A, b, M=None, itmax=0, atol=0.0, rtol=0.0, dt=np.float64):
         cs, sn = gbar / gamma, beta / gamma
         phi = cs * phibar
         phibar = sn * phibar
+        if trace is not None:
+            trace.append((alpha, g, oldeps, delta, gamma, phi))
         w1, w2 = w2, w
         w = ((v - oldeps * w1) - delta * w2) / gamma
         x = x + phi * w
