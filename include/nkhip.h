@@ -45,6 +45,8 @@ extern "C" {
 #define NK_HEAT3D_MIDPOINT 6
 #define NK_HEAT2D_TRAPEZOID 7  /* G_Trapezoid! implicit.jl:29-37                         */
 #define NK_HEAT3D_TRAPEZOID 8
+#define NK_BRATU3D 9       /* build-defined 3D generalisation of NK_BRATU2D ("solid fuel ignition"): one rank,   */
+                           /* bc_zero!; p = (Δx, Δy, Δz, λ)                                      */
 
 #define NK_USER1D 16       /* user residual F!(res, u, p) given as callbacks, */
 #define NK_USER2D 17       /* on a 1D / 2D / 3D grid (the kind fixes the slab axis, as for the      */
@@ -112,7 +114,7 @@ typedef struct nk_user_ops {
  * spacings are global (h = 1/(N_global + 1)).  x is the fastest axis (the reference's
  * column-major first index). */
 typedef struct nk_problem {
-    int32_t kind;           /* NK_BRATU1D … NK_HEAT3D_TRAPEZOID, NK_USER1D … NK_USER3D */
+    int32_t kind;           /* NK_BRATU1D … NK_BRATU3D, NK_USER1D … NK_USER3D */
     int32_t bc;             /* NK_BC_ZERO / NK_BC_PERIODIC */
     int64_t nx, ny, nz;     /* local interior extents (ny = nz = 1 in 1D, nz = 1 in 2D) */
     double hx, hy, hz;      /* grid spacings */

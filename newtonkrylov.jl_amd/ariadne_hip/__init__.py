@@ -13,7 +13,7 @@ from .krylov import (KrylovConstructor, exp_, kaxpby_, kaxpy_, kaxpy_norm_, kcop
                      krylov_workspace, kscal_, mgs_step_)
 from .precond import (DiagonalPreconditioner, GmresPreconditioner, Ilu0Preconditioner, MultigridPreconditioner, Preconditioner,
                       UserPreconditioner, gmres_preconditioner, ilu0, jacobi, jacobian_diag, multigrid, multigrid_plan)
-from .problems import (DeviceResidual, UserResidual, bc_periodic_, bc_zero_, bratu2d_, bratu_, heat2d_euler_, heat2d_midpoint_,
+from .problems import (DeviceResidual, UserResidual, bc_periodic_, bc_zero_, bratu2d_, bratu3d_, bratu_, heat2d_euler_, heat2d_midpoint_,
                        heat2d_trapezoid_, heat3d_euler_, heat3d_midpoint_, heat3d_trapezoid_)
 
 __all__ = [
@@ -24,7 +24,7 @@ __all__ = [
     "DiagonalPreconditioner", "GmresPreconditioner", "Ilu0Preconditioner", "Preconditioner", "UserPreconditioner",
     "gmres_preconditioner", "ilu0", "MultigridPreconditioner", "multigrid", "multigrid_plan",
     "jacobi", "jacobian_diag",
-    "krylov_solve_", "krylov_workspace", "kscal_", "mgs_step_", "DeviceResidual", "UserResidual", "bc_zero_", "bratu2d_", "bratu_",
+    "krylov_solve_", "krylov_workspace", "kscal_", "mgs_step_", "DeviceResidual", "UserResidual", "bc_zero_", "bratu2d_", "bratu3d_", "bratu_",
     "heat2d_euler_", "heat3d_euler_", "heat2d_midpoint_", "heat3d_midpoint_", "heat2d_trapezoid_", "heat3d_trapezoid_",
     "bc_periodic_",
 ]

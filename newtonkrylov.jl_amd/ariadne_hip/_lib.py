@@ -25,6 +25,7 @@ NK_OK = 0
 NK_E_HIP, NK_E_ARG, NK_E_NOMEM, NK_E_RCCL, NK_E_STATE, NK_E_USER = -1, -2, -3, -4, -5, -6
 NK_BRATU1D, NK_BRATU2D, NK_HEAT2D_EULER, NK_HEAT3D_EULER = 1, 2, 3, 4
 NK_HEAT2D_MIDPOINT, NK_HEAT3D_MIDPOINT, NK_HEAT2D_TRAPEZOID, NK_HEAT3D_TRAPEZOID = 5, 6, 7, 8
+NK_BRATU3D = 9
 NK_USER1D, NK_USER2D, NK_USER3D = 16, 17, 18
 NK_BC_ZERO, NK_BC_PERIODIC = 0, 1
 NK_JV_EXACT, NK_JV_FD = 0, 1

@@ -8,6 +8,7 @@ loop, and `JacobianOperator` maps it to the matching fused Jv kernel (nk_jv) ins
 |---------------|-------------------------------------------------------|-------------------------------------|
 | `bratu_`      | `bratu!(res, y, (Δx, λ))`  examples/bratu.jl:14-24    | `(dx, lam)`                          |
 | `bratu2d_`    | 2D generalisation                  | `(dx, dy, lam)`                      |
+| `bratu3d_`    | 3D generalisation of `bratu2d_`       | `(dx, dy, dz, lam)`                  |
 | `heat2d_euler_` | `G_Euler!` ∘ `diffusion!` implicit.jl:8-13 + heat_2D.jl:45-62 | `(u_n, dt, du, (a, dx, dy, bc_zero_), t)` |
 | `heat3d_euler_` | 3D generalisation                | `(u_n, dt, du, (a, dx, dy, dz, bc_zero_), t)` |
 | `heat{2,3}d_midpoint_`, `heat{2,3}d_trapezoid_` | `G_Midpoint!` / `G_Trapezoid!` ∘ `diffusion!` implicit.jl:17-37 | as above; `bc_periodic_` (heat_2D.jl:15-26) for any heat residual |
@@ -76,6 +77,20 @@ class _Bratu2D(DeviceResidual):
         return _lib.nk_problem(self.kind, 0, nx, ny, 1, float(dx), float(dy), 1.0, float(lam), 0.0, 0.0, None)
 
 
+class _Bratu3D(DeviceResidual):
+    """3D Bratu ("solid fuel ignition"): res = ((l_x + l_y) + l_z) + λ exp(u) with l_a = ((u₊ - 2u) + u₋) / (h_a h_a),
+    zero Dirichlet ghosts, one rank."""
+
+    kind, name = _lib.NK_BRATU3D, "bratu3d!"
+
+    def problem(self, u, p):
+        dx, dy, dz, lam = p
+        if u.grid.dim != 3:
+            raise ValueError("bratu3d! needs a 3D grid")
+        nx, ny, nz = u.grid.nxyz
+        return _lib.nk_problem(self.kind, 0, nx, ny, nz, float(dx), float(dy), float(dz), float(lam), 0.0, 0.0, None)
+
+
 def bc_periodic_(u):
     """`bc_periodic!` (heat_2D.jl:15-26): a marker.  The kernels wrap x (and y in 3D) and the library
     fills the ghost planes along the slab axis with the opposite edge (a ring exchange when
@@ -134,6 +149,7 @@ _HeatEuler = _Heat  # backwards-compatible name
 
 bratu_ = _Bratu1D()
 bratu2d_ = _Bratu2D()
+bratu3d_ = _Bratu3D()
 heat2d_euler_ = _Heat(2)
 heat3d_euler_ = _Heat(3)
 heat2d_midpoint_ = _Heat(2, "G_Midpoint!")

@@ -42,7 +42,8 @@ namespace {
 
 template <int KIND>
 constexpr int kind_dim() {
-    return KIND == NK_BRATU1D ? 1 : ((KIND == NK_HEAT3D_EULER || KIND == NK_HEAT3D_MIDPOINT || KIND == NK_HEAT3D_TRAPEZOID) ? 3 : 2);
+    return KIND == NK_BRATU1D ? 1
+                              : ((KIND == NK_HEAT3D_EULER || KIND == NK_HEAT3D_MIDPOINT || KIND == NK_HEAT3D_TRAPEZOID || KIND == NK_BRATU3D) ? 3 : 2);
 }
 template <int KIND>
 constexpr int kind_scheme() {
@@ -50,7 +51,7 @@ constexpr int kind_scheme() {
                ? 1
                : ((KIND == NK_HEAT2D_TRAPEZOID || KIND == NK_HEAT3D_TRAPEZOID) ? 2 : 0);
 }
-constexpr bool kind_bratu(int k) { return k == NK_BRATU1D || k == NK_BRATU2D; }
+constexpr bool kind_bratu(int k) { return k == NK_BRATU1D || k == NK_BRATU2D || k == NK_BRATU3D; }
 
 // ((p - 2c) + m) / h^2 exactly as the reference writes it (bratu.jl:19, heat_2D.jl:55-58)
 __device__ __forceinline__ double lp(double c, double p, double m, double h2) { return ((p - 2.0 * c) + m) / h2; }
@@ -278,7 +279,9 @@ int launch_jv_batch(nk_ctx* c, const nk_problem* p, int nb, double* const* out, 
         case NK_HEAT2D_MIDPOINT: go_batch<NK_HEAT2D_MIDPOINT>(B, mode, grid, s); break;
         case NK_HEAT3D_MIDPOINT: go_batch<NK_HEAT3D_MIDPOINT>(B, mode, grid, s); break;
         case NK_HEAT2D_TRAPEZOID: go_batch<NK_HEAT2D_TRAPEZOID>(B, mode, grid, s); break;
-        default: go_batch<NK_HEAT3D_TRAPEZOID>(B, mode, grid, s); break;
+        case NK_HEAT3D_TRAPEZOID: go_batch<NK_HEAT3D_TRAPEZOID>(B, mode, grid, s); break;
+        case NK_BRATU3D: go_batch<NK_BRATU3D>(B, mode, grid, s); break;
+        default: break;  // (geometry has refused every other kind)
         }
     });
 }

@@ -36,6 +36,10 @@ int geometry(nk_ctx* c, const nk_problem* p, Geo* g) {
     case NK_HEAT3D_TRAPEZOID:
         g->dim = 3; g->plane = p->nx * p->ny; g->nplanes = p->nz;
         break;
+    case NK_BRATU3D:
+        if (c && c->nranks > 1) return fail(c, NK_E_ARG, "3D Bratu runs on one rank (z-slabs and 3D blocks are not implemented for it)");
+        g->dim = 3; g->plane = p->nx * p->ny; g->nplanes = p->nz;
+        break;
     case NK_USER1D:
     case NK_USER2D:
     case NK_USER3D:

@@ -638,9 +638,15 @@ int launch_stencil_ex(nk_ctx* c, const StencilIn& in, Red* red, int rows_overrid
     NK_TRY(geometry(c, p, &g));
     const bool per = p->bc == NK_BC_PERIODIC, blk = blocks3d(c, g);
     const bool vstore = in.vout && in.epi == EPI_DOT;
+    StKnobs knobs = st_knobs();
+    if (p->kind == NK_BRATU3D) {  // k_st3l is the kind's only kernel: the kernel-variant build's k_st3d / k_st3y have no exp
+        knobs.lds3 = 1;
+        knobs.ymarch = 0;
+        fast &= ~524288;
+    }
     const StPlan P = st_plan(StShape{g.dim, p->nx, p->ny, p->nz, per, blk, in.mode, nk_is_heat(p->kind), nk_scheme(p->kind),
                                      vstore, in.aux != nullptr, rows_override, fast, in.f0r},
-                             st_knobs());
+                             knobs);
     KArgs A{};
     A.out = in.out; A.u = in.u; A.v = in.v; A.F0 = in.F0; A.un = p->un; A.aux = in.aux;
     A.nx = p->nx; A.ny = p->ny; A.nz = p->nz;
@@ -717,7 +723,9 @@ int launch_stencil_ex(nk_ctx* c, const StencilIn& in, Red* red, int rows_overrid
         case NK_HEAT2D_MIDPOINT: st = stencil_kind_5(A, mode, epi, vec, grid, s, per); break;
         case NK_HEAT3D_MIDPOINT: st = stencil_kind_6(A, mode, epi, vec, grid, s, per); break;
         case NK_HEAT2D_TRAPEZOID: st = stencil_kind_7(A, mode, epi, vec, grid, s, per); break;
-        default: st = stencil_kind_8(A, mode, epi, vec, grid, s, per); break;
+        case NK_HEAT3D_TRAPEZOID: st = stencil_kind_8(A, mode, epi, vec, grid, s, per); break;
+        case NK_BRATU3D: st = stencil_kind_9(A, mode, epi, vec, grid, s, false); break;
+        default: break;  // (geometry has refused every other kind)
         }
         if (A.group > 1) {  // one-shot tiles: the group sums in tile order, as the next kernel's partials
             const int ng = (grid + A.group - 1) / A.group;

@@ -605,7 +605,7 @@ int mg_free(nk_mg* m) {
     return NK_OK;
 }
 
-bool mg_kind_ok(int kind) { return kind >= NK_BRATU1D && kind <= NK_HEAT3D_TRAPEZOID; }
+bool mg_kind_ok(int kind) { return (kind >= NK_BRATU1D && kind <= NK_HEAT3D_TRAPEZOID) || kind == NK_BRATU3D; }
 
 // diag and 1 / diag of every level from k and s_0 (already in m->s[0]); level 0's from nk_jacobian_diag when
 // `jac` (bit-identical to J's own diagonal); then the sign check that may truncate the hierarchy
@@ -866,7 +866,7 @@ int nk_mg_set_jacobian(nk_mg* m, const nk_problem* p, const double* u) {
         const double theta = sch == 1 ? 1.0 - p->alpha : (sch == 2 ? 0.5 : 1.0);
         for (int a = 0; a < m->dim; ++a) k[a] = theta * p->a * p->dt;
         NK_TRY(launch_fill(c, n, m->s[0], -1.0));
-    } else {
+    } else {  // NK_BRATU1D / 2D / 3D: the Laplacian plus s = λ exp(u)
         for (int a = 0; a < m->dim; ++a) k[a] = 1.0;
         NK_TRY(launch_exp(c, n, m->s[0], u));  // the stencils' own correctly rounded exp
         NK_TRY(launch_scal(c, n, p->lambda, m->s[0]));

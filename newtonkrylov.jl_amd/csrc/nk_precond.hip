@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void k_jdiag(KArgs A, double* __restrict__ 
         double lsum = lapk(A, c, 0.0, 0.0, A.hx2, A.ihx2);
         if (DIM >= 2) lsum = lsum + lapk(A, c, 0.0, 0.0, A.hy2, A.ihy2);
         if (DIM == 3) lsum = lsum + lapk(A, c, 0.0, 0.0, A.hz2, A.ihz2);
-        const double uc = (KIND == NK_BRATU1D || KIND == NK_BRATU2D) ? A.u[i] : 0.0;
+        const double uc = kind_bratu(KIND) ? A.u[i] : 0.0;
         bool rare_ = false;
         const double d = point_value<KIND, MODE_JEXACT>(A, c, lsum, uc, 0.0, 0.0, 1.0, 0.0, &NKX_T[0][0], rare_);
         out[i] = recip ? 1.0 / d : d;
@@ -102,7 +102,9 @@ int launch_jdiag(nk_ctx* c, const nk_problem* p, double* out, const double* u, i
         case NK_HEAT2D_TRAPEZOID: NK_JDIAG(NK_HEAT2D_TRAPEZOID, 2); break;
         case NK_HEAT3D_MIDPOINT: NK_JDIAG(NK_HEAT3D_MIDPOINT, 3); break;
         case NK_HEAT3D_TRAPEZOID: NK_JDIAG(NK_HEAT3D_TRAPEZOID, 3); break;
-        default: NK_JDIAG(NK_HEAT3D_EULER, 3); break;
+        case NK_HEAT3D_EULER: NK_JDIAG(NK_HEAT3D_EULER, 3); break;
+        case NK_BRATU3D: NK_JDIAG(NK_BRATU3D, 3); break;
+        default: break;  // (geometry has refused every other kind)
         }
     });
 #undef NK_JDIAG

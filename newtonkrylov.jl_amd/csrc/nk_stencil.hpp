@@ -78,11 +78,12 @@ NK_ST_DECL(5)
 NK_ST_DECL(6)
 NK_ST_DECL(7)
 NK_ST_DECL(8)
+NK_ST_DECL(9)
 #undef NK_ST_DECL
 
 namespace {
 
-// implicit.jl scheme of a heat kind: 0 G_Euler! (and the Bratu kinds), 1 G_Midpoint!, 2 G_Trapezoid!
+// implicit.jl scheme of a heat kind: 0 G_Euler! (and the Bratu kinds, NK_BRATU3D included), 1 G_Midpoint!, 2 G_Trapezoid!
 template <int KIND>
 constexpr int scheme_of() {
     return (KIND == NK_HEAT2D_MIDPOINT || KIND == NK_HEAT3D_MIDPOINT)
@@ -90,14 +91,18 @@ constexpr int scheme_of() {
                : ((KIND == NK_HEAT2D_TRAPEZOID || KIND == NK_HEAT3D_TRAPEZOID) ? 2 : 0);
 }
 template <int KIND>
-constexpr bool heat_kind() {
+constexpr bool heat_kind() {  // (NK_BRATU3D = 9 lies beyond the heat range)
     return KIND >= NK_HEAT2D_EULER && KIND <= NK_HEAT3D_TRAPEZOID;
 }
 
 // div_rn is used in the Bratu stencil objects only (nk_stencil_inst.hip with NK_ST_KIND 1 / 2: their FD Jv
 // 130 -> 126 us, profiles/r04/ab_div_rn.log); elsewhere its guard's compares and exec-mask branches cost
 // more than the division sequence they replace (the heat2d FD Jv loop: 304 -> 471 instructions).
-#if defined(NK_ST_KIND) && (NK_ST_KIND == NK_BRATU1D || NK_ST_KIND == NK_BRATU2D)
+// NK_BRATU3D's object: NK_ST3D_BRATU_DIV_RN (a `make variant` define for the A/B)
+#ifndef NK_ST3D_BRATU_DIV_RN
+#define NK_ST3D_BRATU_DIV_RN 1
+#endif
+#if defined(NK_ST_KIND) && (NK_ST_KIND == NK_BRATU1D || NK_ST_KIND == NK_BRATU2D || (NK_ST_KIND == NK_BRATU3D && NK_ST3D_BRATU_DIV_RN))
 #define NK_ST_DIV_RN 1
 #else
 #define NK_ST_DIV_RN 0
@@ -190,7 +195,7 @@ __device__ __forceinline__ void storevec(double* __restrict__ p, int64_t o, cons
     }
 }
 
-constexpr bool kind_bratu(int k) { return k == NK_BRATU1D || k == NK_BRATU2D; }
+constexpr bool kind_bratu(int k) { return k == NK_BRATU1D || k == NK_BRATU2D || k == NK_BRATU3D; }
 // A/B only (-DNK_ST_KEEP_VDIV): keep the runtime v / h test in every instantiation (round 3's form, where
 // the instances without the fused normalisation evaluated the division and discarded it)
 #ifdef NK_ST_KEEP_VDIV
@@ -245,7 +250,7 @@ constexpr int st2d_wpe(int kind, int mode, bool f0r) {
 template <int KIND, int MODE, int XM = 0>
 __device__ __forceinline__ double point_value(const KArgs& A, double c, double lsum, double uc, double unc, double f0c,
                                               double xc, double lsumg, const double* et, bool& rare) {
-    if constexpr (KIND == NK_BRATU1D || KIND == NK_BRATU2D) {
+    if constexpr (kind_bratu(KIND)) {
 #ifdef NK_KBENCH
         if (A.fast & (1 << 20)) {  // kbench A/B only: the platform (ocml) exp, <= 1 ulp off the correctly rounded one
             if (MODE == MODE_JEXACT) return lsum + A.lam * (exp(uc) * c);

@@ -331,8 +331,16 @@ __device__ bool blk_tile_exchange(const KArgs& A, int tx, int ty, int tz, int64_
 // with F(u) recomputed -- the config-5 slab's Jv, 147 -> 141 us; every other instance unconstrained (the
 // same cap on all of them: 512^3 Euler FD Jv 1160 -> 1257 us, midpoint 1303 -> 2900 us with spills,
 // profiles/r04/ab_st3l_wpe.log)
+// NK_BRATU3D: 3 waves per SIMD (<= 168 VGPRs) for every instance.  Unconstrained, the VEC 2 instances take 118
+// (residual) to 164 (FD Jv + dot with V_k stored) VGPRs and no scratch, i.e. 3 waves for every Jv -- what the heat
+// instances of this march run at; the 2D Bratu march's 4-wave cap (<= 128) spills 12 to 56 VGPRs in every VEC 2 FD
+// instance here, and the spills of a capped z-march are what cost the heat kinds 8 % to 2.2x (above).  DESIGN.md §12.
+#ifndef NK_ST3L_BRATU_WPE
+#define NK_ST3L_BRATU_WPE 3
+#endif
 #ifndef NK_ST3L_WPE
-#define NK_ST3L_WPE(KIND, EPI, F0R, BLK) ((KIND == NK_HEAT3D_EULER && EPI == EPI_DOT && F0R && NK_ST3L_WPE_BLK(BLK)) ? 4 : 1)
+#define NK_ST3L_WPE(KIND, EPI, F0R, BLK) \
+    (KIND == NK_BRATU3D ? NK_ST3L_BRATU_WPE : ((KIND == NK_HEAT3D_EULER && EPI == EPI_DOT && F0R && NK_ST3L_WPE_BLK(BLK)) ? 4 : 1))
 #endif
 #ifndef NK_ST3L_BLK_CAP  // (product variant build for A/B: 1 = the 4-wave cap for the BLK instance too)
 #define NK_ST3L_BLK_CAP 0
@@ -345,7 +353,15 @@ __device__ bool blk_tile_exchange(const KArgs& A, int tx, int ty, int tz, int64_
 template <int KIND, int MODE, int EPI, int VEC, bool PER = false, int NW = 8, bool F0R = false, bool BLK = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NK_ST3L_WPE(KIND, EPI, F0R, BLK)))) void k_st3l(KArgs A0) {
     __shared__ double sh[kShN];
-    const double* const et = nullptr;  // heat kinds: no exp
+    const double* et = nullptr;  // heat kinds: no exp
+    if constexpr (kind_bratu(KIND)) {  // NK_BRATU3D: the exp table in LDS, as NK_EXP_LDS copies it for the 1D / 2D kinds
+        __shared__ double et_lds[256];
+        for (int i_ = threadIdx.x; i_ < 256; i_ += blockDim.x) et_lds[i_] = (&NKX_T[0][0])[i_];
+        __syncthreads();
+        et = et_lds;
+    }
+    // the exp per lane in one pass, as the 2D Bratu march: the fast phase, the exact phase in the rare lanes
+    constexpr int XM = kind_bratu(KIND) ? 2 : 0;
     bool rare_ = false;
     KArgs A = A0;
     if constexpr (!kKeepVdiv && EPI != EPI_DOTV && EPI != EPI_DOTVS) A.vdiv = nullptr;  // v / h only with V_k stored
@@ -423,7 +439,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NK_ST3L
 #endif
     const int64_t st = dn ? -pl : pl, dz = dn ? -1 : 1;
     const int64_t zs = dn ? z1 - 1 : z0;
-    constexpr bool kUn = SCH == 0 && MODE != MODE_JEXACT;
+    constexpr bool kUn = SCH == 0 && MODE != MODE_JEXACT && !kind_bratu(KIND);  // G_Euler!'s u_n (Bratu has none)
+    constexpr bool kU = MODE == MODE_JEXACT && kind_bratu(KIND);  // the centre of u for the tangent of λ exp(u)
     constexpr bool kF0 = MODE == MODE_JFD && !kR;
     constexpr bool kAx = EPI == EPI_DOT || EPI == EPI_DOTV || EPI == EPI_RESID;
     constexpr bool vout = MODE != MODE_RES && (EPI == EPI_DOTV || EPI == EPI_DOTVS);
@@ -484,7 +501,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NK_ST3L
         RawRow<MODE, VEC> rn{}, rs{};
         if (ld_n) rn = load_raw<MODE, VEC, false, kG, kE2>(A, nrow(zs, o0), 0);
         if (ld_s) rs = load_raw<MODE, VEC, false, kG, kE2>(A, srow(zs, o0), 0);
-        Row<VEC> unc{}, f0c{}, ax{};
+        Row<VEC> uc{}, unc{}, f0c{}, ax{};
+        if constexpr (kU) uc = data_row<VEC>(A.u, o0, true);
         if constexpr (kUn) unc = data_row<VEC, NK_ST_NTN>(A.un, o0, true);
         if constexpr (kF0) f0c = data_row<VEC, NK_ST_NT>(A.F0, o0, true);
         if constexpr (kAx) ax = data_row<VEC>(A.aux, o0, true);
@@ -510,7 +528,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NK_ST3L
             const int64_t k1 = more ? k + dz : k;  // the plane o1 is in
             if (ld_n) rnn = load_raw<MODE, VEC, false, kG, kE2>(A, nrow(k1, o1), 0);
             if (ld_s) rss = load_raw<MODE, VEC, false, kG, kE2>(A, srow(k1, o1), 0);
-            Row<VEC> uncn{}, f0cn{}, axn{};
+            Row<VEC> ucn{}, uncn{}, f0cn{}, axn{};
+            if constexpr (kU) ucn = data_row<VEC>(A.u, o1, true);
             if constexpr (kUn) uncn = data_row<VEC, NK_ST_NTN>(A.un, o1, true);
             if constexpr (kF0) f0cn = data_row<VEC, NK_ST_NT>(A.F0, o1, true);
             if constexpr (kAx) axn = data_row<VEC>(A.aux, o1, true);
@@ -586,9 +605,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NK_ST3L
                         const double ucc = uc_.c[q];
                         const double lsu = (lapk(A, ucc, ue, uw, A.hx2, A.ihx2) + lapk(A, ucc, cnu[q], csu[q], A.hy2, A.ihy2)) +
                                            lapk(A, ucc, dn ? um.c[q] : up.c[q], dn ? up.c[q] : um.c[q], A.hz2, A.ihz2);
-                        f0 = point_value<KIND, MODE_RES>(A, ucc, lsu, 0.0, unq, 0.0, SCH == 1 ? uc_.x[q] : ucc, lsumg, et, rare_);
+                        f0 = point_value<KIND, MODE_RES, XM>(A, ucc, lsu, 0.0, unq, 0.0, SCH == 1 ? uc_.x[q] : ucc, lsumg, et, rare_);
                     }
-                    double r = point_value<KIND, MODE>(A, c, lsum, 0.0, unq, f0, SCH == 1 ? fc.x[q] : c, lsumg, et, rare_);
+                    double r = point_value<KIND, MODE, XM>(A, c, lsum, uc.v[q], unq, f0, SCH == 1 ? fc.x[q] : c, lsumg, et, rare_);
                     acc = epilogue<EPI>(r, EPI == EPI_DOTVS ? fc.vn[q] : ax.v[q], acc);
                     val.v[q] = r;
                 }
@@ -609,6 +628,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NK_ST3L
             rp = rpp;
             rn = rnn;
             rs = rss;
+            uc = ucn;
             unc = uncn;
             f0c = f0cn;
             ax = axn;
@@ -656,26 +676,31 @@ StInst go_st3l(const KArgs& A, int vec, int grid, hipStream_t s, bool per) {
 #else
     constexpr bool kF0R = MODE == MODE_JFD && KIND == NK_HEAT3D_EULER;  // the only 3D F0R kind the launcher picks
 #endif
-    if (A.blk) {  // 3D blocks: bc_zero! only
-        if constexpr (kF0R) {
-            if (A.f0r) return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, false, NW, true, true>(A, grid, s)
-                                       : go_st3l_i<KIND, MODE, EPI, 1, false, NW, true, true>(A, grid, s);
+    if constexpr (kind_bratu(KIND)) {  // NK_BRATU3D: one rank, bc_zero! (geometry refuses the rest): no PER / BLK instance
+        return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, false, NW, false>(A, grid, s)
+                        : go_st3l_i<KIND, MODE, EPI, 1, false, NW, false>(A, grid, s);
+    } else {
+        if (A.blk) {  // 3D blocks: bc_zero! only
+            if constexpr (kF0R) {
+                if (A.f0r) return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, false, NW, true, true>(A, grid, s)
+                                           : go_st3l_i<KIND, MODE, EPI, 1, false, NW, true, true>(A, grid, s);
+            }
+            return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, false, NW, false, true>(A, grid, s)
+                            : go_st3l_i<KIND, MODE, EPI, 1, false, NW, false, true>(A, grid, s);
         }
-        return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, false, NW, false, true>(A, grid, s)
-                        : go_st3l_i<KIND, MODE, EPI, 1, false, NW, false, true>(A, grid, s);
-    }
-    if constexpr (kF0R) {  // F0 recomputed from u (KArgs::f0r)
-        if (A.f0r) {
-            if (per) return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, true, NW, true>(A, grid, s)
-                                     : go_st3l_i<KIND, MODE, EPI, 1, true, NW, true>(A, grid, s);
-            return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, false, NW, true>(A, grid, s)
-                            : go_st3l_i<KIND, MODE, EPI, 1, false, NW, true>(A, grid, s);
+        if constexpr (kF0R) {  // F0 recomputed from u (KArgs::f0r)
+            if (A.f0r) {
+                if (per) return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, true, NW, true>(A, grid, s)
+                                         : go_st3l_i<KIND, MODE, EPI, 1, true, NW, true>(A, grid, s);
+                return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, false, NW, true>(A, grid, s)
+                                : go_st3l_i<KIND, MODE, EPI, 1, false, NW, true>(A, grid, s);
+            }
         }
+        if (per) return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, true, NW, false>(A, grid, s)
+                                 : go_st3l_i<KIND, MODE, EPI, 1, true, NW, false>(A, grid, s);
+        return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, false, NW, false>(A, grid, s)
+                        : go_st3l_i<KIND, MODE, EPI, 1, false, NW, false>(A, grid, s);
     }
-    if (per) return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, true, NW, false>(A, grid, s)
-                             : go_st3l_i<KIND, MODE, EPI, 1, true, NW, false>(A, grid, s);
-    return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, false, NW, false>(A, grid, s)
-                    : go_st3l_i<KIND, MODE, EPI, 1, false, NW, false>(A, grid, s);
 }
 
 }  // namespace
@@ -721,7 +746,9 @@ StInst go_stencil(const KArgs& A, int vec, int grid, hipStream_t s, bool per) {
         // k_st3l: y-neighbours through LDS, 4-row tiles (the kernel-variant build: 8-row tiles, the
         // per-wave y-row loads of k_st3d, the y-march k_st3y)
 #ifdef NK_KBENCH
-        if (!A.blk) {  // (3D blocks: k_st3l with 4-row tiles only)
+        if constexpr (kind_bratu(KIND)) {  // NK_BRATU3D: k_st3l only (launch_stencil_ex plans nothing else for it)
+            if (A.nw == 8) return go_st3l<KIND, MODE, EPI, 8>(A, vec, grid, s, per);
+        } else if (!A.blk) {  // (3D blocks: k_st3l with 4-row tiles only)
             if (A.ym) return A.nw == 8 ? go_st3y<KIND, MODE, EPI, 8>(A, vec, grid, s, per)
                                        : go_st3y<KIND, MODE, EPI, 4>(A, vec, grid, s, per);
             if (!A.lds3) return go_st3d<KIND, MODE, EPI, 4>(A, vec, grid, s, per);

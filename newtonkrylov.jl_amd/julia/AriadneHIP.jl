@@ -17,6 +17,7 @@ const libnkhip = joinpath(@__DIR__, "..", "lib", "libnkhip.so")
 
 const NK_BRATU1D, NK_BRATU2D, NK_HEAT2D_EULER, NK_HEAT3D_EULER = Int32(1), Int32(2), Int32(3), Int32(4)
 const NK_HEAT2D_MIDPOINT, NK_HEAT3D_MIDPOINT, NK_HEAT2D_TRAPEZOID, NK_HEAT3D_TRAPEZOID = Int32(5), Int32(6), Int32(7), Int32(8)
+const NK_BRATU3D = Int32(9)
 const NK_BC_ZERO, NK_BC_PERIODIC = Int32(0), Int32(1)
 const NK_USER1D, NK_USER2D, NK_USER3D = Int32(16), Int32(17), Int32(18)
 const NK_JV_EXACT, NK_JV_FD = Int32(0), Int32(1)
@@ -207,6 +208,7 @@ end
 HipResidual{K}(; jv::Integer = NK_JV_EXACT, α::Real = 0.5) where {K} = HipResidual{K}(Int32(jv), Float64(α))
 const bratu! = HipResidual{:bratu1d}()        # examples/bratu.jl:14-24, p = (Δx, λ)
 const bratu2d! = HipResidual{:bratu2d}()      # p = (Δx, Δy, λ)
+const bratu3d! = HipResidual{:bratu3d}()      # p = (Δx, Δy, Δz, λ); one rank
 # G ∘ diffusion! (implicit.jl:8-37 ∘ heat_2D.jl:45-62), p = (uₙ, Δt, du, (a, Δx, Δy, bc!), t); 3D: (a, Δx, Δy, Δz, bc!)
 const heat2d_euler! = HipResidual{:heat2d}()
 const heat2d_midpoint! = HipResidual{:heat2d_midpoint}()    # α = 0.5; HipResidual{:heat2d_midpoint}(α = 0.3)
@@ -222,6 +224,7 @@ const HEAT_KINDS = (heat2d = NK_HEAT2D_EULER, heat2d_midpoint = NK_HEAT2D_MIDPOI
 
 problem(F::HipResidual{:bratu1d}, u::HipVector, (dx, λ)) = NkProblem(NK_BRATU1D, 0, u.grid..., dx, 1, 1, λ, 0, 0, C_NULL, C_NULL, F.α)
 problem(F::HipResidual{:bratu2d}, u::HipVector, (dx, dy, λ)) = NkProblem(NK_BRATU2D, 0, u.grid..., dx, dy, 1, λ, 0, 0, C_NULL, C_NULL, F.α)
+problem(F::HipResidual{:bratu3d}, u::HipVector, (dx, dy, dz, λ)) = NkProblem(NK_BRATU3D, 0, u.grid..., dx, dy, dz, λ, 0, 0, C_NULL, C_NULL, F.α)
 function problem(F::HipResidual{K}, u::HipVector, (un, Δt, _, fp, _t)) where {K}
     kind = HEAT_KINDS[K]
     three = kind in (NK_HEAT3D_EULER, NK_HEAT3D_MIDPOINT, NK_HEAT3D_TRAPEZOID)
