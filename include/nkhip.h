@@ -270,8 +270,30 @@ typedef struct nk_mg_opts {
 /* the level extents of a grid (host only, no GPU): extents[3 l + a] = n_a of level l (1 for unused axes),
  * at most cap levels written, *nlevels = the number of levels */
 int nk_mg_plan(const int64_t n[3], int32_t max_levels, int64_t* extents, int32_t cap, int32_t* nlevels);
-/* opts may be null (the defaults).  NK_E_ARG for periodic boundaries, a distributed context, NK_USER* kinds */
+/* opts may be null (the defaults).  NK_E_ARG for periodic boundaries and NK_USER* kinds.
+ *
+ * On a distributed context (nk_dist_init / nk_dist_mailbox_open) the hierarchy is the slab-distributed one: the 2D
+ * and 3D built-in kinds the slabs run (NK_BRATU2D, every NK_HEAT2D_* and NK_HEAT3D_* kind), bc_zero!, y- / z-slabs.
+ * PRECONDITION: EQUAL SLABS -- every rank passes the same local extents, and the global extent of the slowest axis
+ * is nranks x the local one (the library sees only local extents and cannot check this).  Each level's rows are
+ * split over the ranks: level l + 1 exists only while the local slab extent m_l is even, m_{l+1} = m_l / 2 (down to
+ * one plane per rank; opts->max_levels caps it further).  So the cycle is the one-rank cycle of the global grid with
+ * max_levels = that count L_d, bit for bit; its coarsest level runs coarse_sweeps sweeps (raise them on many ranks:
+ * DESIGN.md §10 gives the cost of cutting the hierarchy short).  nk_mg_plan_slabs gives the plan.  The level arrays
+ * carry one ghost plane on each side of the slab axis, refreshed by the context's ghost-plane exchange before every
+ * launch that reads neighbours along it.  nk_mg_create, nk_mg_set_jacobian and nk_mg_set_operator are COLLECTIVE
+ * then (every rank calls them, in the same order; the latter two agree across the ranks on where set-up truncates
+ * the hierarchy); nk_mg_apply / nk_mg_apply_dot must be called by every rank as well (they exchange ghost planes).
+ * nk_mg_levels and nk_mg_level_extents report LOCAL extents (global along the slab axis: nranks x).  s_dev of
+ * nk_mg_set_operator is this rank's slab.  NK_E_ARG naming the reason, on every rank alike and before anything is
+ * exchanged: periodic boundaries, 3D blocks (nk_dist_grid with px py > 1), 1D kinds, NK_BRATU3D, NK_USER* kinds,
+ * nk_mg_create_levels (semicoarsening), an odd local slab extent. */
 int nk_mg_create(nk_ctx* ctx, const nk_problem* p, const nk_mg_opts* opts, nk_mg** out);
+/* the plan of a slab-distributed hierarchy in LOCAL extents (host only, no GPU; output as nk_mg_plan): n_local = one
+ * rank's extents (equal slabs), nranks >= 2.  NK_E_ARG where nk_mg_create would refuse the grid: a 1D grid, an odd
+ * local slab extent, nranks < 2. */
+int nk_mg_plan_slabs(const int64_t n_local[3], int32_t nranks, int32_t max_levels, int64_t* extents, int32_t cap,
+                     int32_t* nlevels);
 /* Semicoarsening, for grids and coefficients whose couplings c_a = |k_a| / h_a^2 differ between the axes (point
  * Jacobi with full coarsening does not damp the error that is smooth along the strong axis only).  The plan (host
  * only, no GPU; output as nk_mg_plan): with L_a = (n_a + 1) h_a of level 0, on every level c_a = |k_a| ((n_a + 1) /

@@ -168,11 +168,21 @@ class MultigridPreconditioner(Preconditioner):
     square: 16384 x 2048 has c_x = 64 c_y) or, with from_coefficients, when k does: point Jacobi with full
     coarsening does not damp the error that is smooth along the strong axis only, and the Krylov step count grows
     with the ratio.  Where the couplings are within a factor 1 / threshold of each other both give
-    the same levels.  The default stays "full"."""
+    the same levels.  The default stays "full".
+
+    `distributed=True`: the hierarchy on a slab-distributed grid (`ah.slab` on a context of several ranks, equal
+    slabs: the global extent of the slowest axis is nranks x the local one).  Each level's rows are split over the
+    ranks; level l + 1 exists only while the local slab extent is even (`multigrid_plan(local, nranks=R)`), so the
+    cycle is the one-rank cycle of the global grid with `max_levels` = that count, bit for bit, and its coarsest
+    level runs `coarse_sweeps` sweeps -- raise them on many ranks.  Construction, `update` and
+    `set_coefficients` are collective, and every rank must apply the cycle; `levels` reports local extents.  2D and
+    3D built-in kinds, bc_zero_, full coarsening, no 3D blocks.  Without the flag a distributed context or a slab
+    keeps raising NotImplementedError."""
 
     def __init__(self, J, nu: int = 2, coarse_sweeps: int = 8, omega: float | None = None, max_levels: int = 0,
-                 spd: bool = False, coarsening: str = "full", threshold: float = 0.5):
-        prob = _mg_problem(J)
+                 spd: bool = False, coarsening: str = "full", threshold: float = 0.5, distributed: bool = False):
+        self.distributed = bool(distributed)
+        prob = _mg_problem(J, distributed, coarsening)
         # the built-in Jacobians have the same k on every axis: the plan depends on the spacings alone
         self._create(J.u.ctx, J.u.grid, prob, nu, coarse_sweeps, omega, max_levels, coarsening, threshold, None)
         self.spd = spd
@@ -201,23 +211,28 @@ class MultigridPreconditioner(Preconditioner):
     @classmethod
     def from_coefficients(cls, grid, k, s, *, h=None, ctx=None, nu: int = 2, coarse_sweeps: int = 8,
                           omega: float | None = None, max_levels: int = 0, spd: bool = False, coarsening: str = "full",
-                          threshold: float = 0.5):
+                          threshold: float = 0.5, distributed: bool = False):
         """The V-cycle for A = Σ_a k[a] δ²_a(h[a]) + diag(s) on `grid` with caller-supplied coefficients: k per
         axis, s a DeviceArray on the grid or a constant; h = the spacings (default 1 / (n + 1) per axis).  Such an
         object keeps the caller's operator: the Newton drivers do not refresh it from the Jacobian (so it also
         serves a UserResidual); call update(J) yourself to switch it to a built-in J's coefficients.
-        coarsening="semi": the plan is made from this k and h (a later set_coefficients keeps it)."""
+        coarsening="semi": the plan is made from this k and h (a later set_coefficients keeps it).
+        distributed=True: `grid` is this rank's slab (ah.slab, equal slabs) and s its slab of the coefficient; the
+        default spacings are those of the global grid."""
         from .device import default_context
 
         _mg_coarsening(coarsening, threshold)
         self = cls.__new__(cls)
+        self.distributed = bool(distributed)
         ctx = ctx or (s.ctx if isinstance(s, DeviceArray) else default_context())
-        if getattr(ctx, "nranks", 1) != 1 or tuple(grid.shape_xyz) != tuple(grid.global_xyz):
-            raise NotImplementedError("multigrid: one rank only (a distributed grid is not implemented)")
+        if distributed:
+            _mg_slab_check(ctx, grid, coarsening)
+        elif getattr(ctx, "nranks", 1) != 1 or tuple(grid.shape_xyz) != tuple(grid.global_xyz):
+            raise NotImplementedError("multigrid: one rank only (a distributed grid needs distributed=True)")
         k = [float(x) for x in (k if hasattr(k, "__len__") else [k] * grid.dim)]
         if len(k) != grid.dim:
             raise ValueError("k: one coefficient per axis")
-        h = [float(x) for x in (h if h is not None else [1.0 / (n + 1) for n in grid.shape_xyz])]
+        h = [float(x) for x in (h if h is not None else [1.0 / (n + 1) for n in grid.global_xyz])]
         if len(h) != grid.dim:
             raise ValueError("h: one spacing per axis")
         if isinstance(s, DeviceArray) and s.grid != grid:
@@ -249,7 +264,7 @@ class MultigridPreconditioner(Preconditioner):
         """k and s of J(u) at J's current u (nk_mg_set_jacobian): call after u changed."""
         import ctypes as C
 
-        prob = _mg_problem(J)
+        prob = _mg_problem(J, getattr(self, "distributed", False))
         self.caller_operator = False
         if J.u.grid != self.grid or J.u.ctx is not self.ctx:
             raise ValueError("multigrid: J lives on another grid / context than the hierarchy")
@@ -311,7 +326,28 @@ class MultigridPreconditioner(Preconditioner):
             pass
 
 
-def _mg_problem(J):
+def _mg_slab_check(ctx, grid, coarsening="full"):
+    """distributed=True: what the slab-distributed hierarchy needs of the context and the grid (values every rank
+    holds alike); NotImplementedError naming the reason otherwise"""
+    nranks = getattr(ctx, "nranks", 1)
+    if nranks <= 1:
+        raise NotImplementedError("multigrid: distributed=True needs a context of several ranks (nranks == 1: leave it out)")
+    pgrid = getattr(ctx, "pgrid", None)
+    if grid.origin is not None or (pgrid is not None and pgrid[0] * pgrid[1] > 1):
+        raise NotImplementedError("multigrid: distributed=True covers slabs (3D blocks are not implemented)")
+    if grid.dim == 1:
+        raise NotImplementedError("multigrid: distributed=True covers 2D and 3D grids (1D kinds are not distributed)")
+    if coarsening != "full":
+        raise NotImplementedError('multigrid: coarsening="semi" is not implemented with distributed=True')
+    loc, glob = tuple(grid.shape_xyz), tuple(grid.global_xyz)
+    if loc[:-1] != glob[:-1] or glob[-1] != nranks * loc[-1]:
+        raise NotImplementedError("multigrid: distributed=True needs equal slabs of the slowest axis over the context's "
+                                  f"{nranks} ranks (uneven slabs are not implemented): local {loc}, global {glob}")
+    if loc[-1] % 2:
+        raise NotImplementedError("multigrid: slabs of an odd number of planes cannot be coarsened")
+
+
+def _mg_problem(J, distributed=False, coarsening="full"):
     """J's nk_problem if the multigrid preconditioner covers it; NotImplementedError naming the reason if not
     (checked on the host, before anything touches the device)."""
     from .problems import UserResidual
@@ -320,11 +356,15 @@ def _mg_problem(J):
         raise NotImplementedError("multigrid: a user residual has no known stencil coefficients -- build the V-cycle "
                                   "with MultigridPreconditioner.from_coefficients(grid, k, s)")
     ctx, grid = J.u.ctx, J.u.grid
-    if getattr(ctx, "nranks", 1) != 1 or tuple(grid.shape_xyz) != tuple(grid.global_xyz):
-        raise NotImplementedError("multigrid: one rank only (a distributed context / slab is not implemented)")
+    if distributed:
+        _mg_slab_check(ctx, grid, coarsening)
+    elif getattr(ctx, "nranks", 1) != 1 or tuple(grid.shape_xyz) != tuple(grid.global_xyz):
+        raise NotImplementedError("multigrid: one rank only (a distributed context / slab needs distributed=True)")
     prob = J.problem()
     if prob.bc != _lib.NK_BC_ZERO:
         raise NotImplementedError("multigrid: bc_zero_ only (periodic boundaries are not implemented)")
+    if distributed and prob.kind == _lib.NK_BRATU3D:
+        raise NotImplementedError("multigrid: 3D Bratu runs on one rank (distributed=True is not implemented for it)")
     return prob
 
 
@@ -338,10 +378,13 @@ def _mg_coarsening(coarsening, threshold):
     return coarsening, threshold
 
 
-def multigrid_plan(shape_xyz, max_levels: int = 0, *, coarsening: str = "full", h=None, k=None, threshold: float = 0.5) -> list:
+def multigrid_plan(shape_xyz, max_levels: int = 0, *, coarsening: str = "full", h=None, k=None, threshold: float = 0.5,
+                   nranks: int = 1) -> list:
     """The level extents of a grid (host only, no GPU): [(nx[, ny[, nz]]), ...].  coarsening="full": nk_mg_plan.
     "semi": nk_mg_plan_semi with the spacings h (default 1 / (n + 1) per axis), the coefficients k per axis
-    (default all ones) and the threshold (MultigridPreconditioner)."""
+    (default all ones) and the threshold (MultigridPreconditioner).  nranks > 1: the plan of the slab-distributed
+    hierarchy (distributed=True; nk_mg_plan_slabs) -- shape_xyz is one rank's LOCAL extents (equal slabs), and so
+    are the levels; NotImplementedError where no such hierarchy exists (an odd local slab extent, a 1D grid)."""
     import ctypes as C
 
     coarsening, threshold = _mg_coarsening(coarsening, threshold)
@@ -349,6 +392,13 @@ def multigrid_plan(shape_xyz, max_levels: int = 0, *, coarsening: str = "full", 
     n = (C.c_int64 * 3)(*(list(shape_xyz) + [1, 1])[:3])
     ext = (C.c_int64 * (3 * 64))()
     nl = C.c_int32(0)
+    if int(nranks) != 1:
+        if coarsening != "full":
+            raise NotImplementedError('multigrid: coarsening="semi" is not implemented on slabs (nranks > 1)')
+        if load().nk_mg_plan_slabs(n, int(nranks), int(max_levels), ext, 64, C.byref(nl)) != 0:
+            raise NotImplementedError(f"multigrid: no slab plan for local extents {tuple(shape_xyz)} on {nranks} ranks (slabs "
+                                      "of an odd number of planes cannot be coarsened; 2D and 3D grids, nranks >= 2)")
+        return [tuple(int(ext[3 * l + a]) for a in range(dim)) for l in range(min(nl.value, 64))]
     if coarsening == "semi":
         hh = [float(x) for x in (h if h is not None else [1.0 / (m + 1) for m in shape_xyz])]
         kk = [float(x) for x in (k if k is not None else [1.0] * dim)]
@@ -370,8 +420,8 @@ class _MultigridFactory:
         self.opts, self.key, self.mg = dict(opts), None, None
 
     def __call__(self, J):
-        prob = _mg_problem(J)
-        key = (id(J.u.ctx), J.u.grid, prob.kind, prob.hx, prob.hy, prob.hz)
+        prob = _mg_problem(J, self.opts.get("distributed", False), self.opts.get("coarsening", "full"))
+        key = (id(J.u.ctx), J.u.grid, prob.kind, prob.hx, prob.hy, prob.hz)  # (the options are the factory's own)
         if self.mg is None or self.key != key or self.mg.handle is None or self.mg.ctx is not J.u.ctx:
             self.free()
             self.key, self.mg = key, MultigridPreconditioner(J, **self.opts)
@@ -391,7 +441,8 @@ def multigrid(J=None, **opts):
     `multigrid(...)` keeps its hierarchy for as long as it lives (`.free()` releases it); `N=multigrid` itself
     keeps nothing beyond the solve.  Called with an operator, `multigrid(J)` is MultigridPreconditioner(J).
     `M=multigrid(spd=True)` is the SPD form, CG's and MINRES's preconditioner (algo="cg" / "minres"); `N=multigrid(coarsening="semi")` the
-    semicoarsened hierarchy for grids whose spacings differ between the axes (MultigridPreconditioner)."""
+    semicoarsened hierarchy for grids whose spacings differ between the axes (MultigridPreconditioner);
+    `N=multigrid(distributed=True)` the hierarchy on equal slabs of a distributed context (every rank builds one)."""
     if J is None:
         _mg_coarsening(opts.get("coarsening", "full"), opts.get("threshold", 0.5))
         return _MultigridFactory(opts)

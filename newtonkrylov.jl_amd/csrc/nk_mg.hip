@@ -7,7 +7,10 @@
 // level of at most kMgTailPoints points, all of them in one work-group's LDS, one launch).  The level extents are a
 // plan: mg_plan halves every axis of more than 3 points, mg_plan_semi only the strongly coupled ones (anisotropic
 // grids and coefficients), nk_mg_create_levels takes any such list; the transfers between two levels that coarsen a
-// proper subset of the axes run kernels instantiated on that subset (k_mg_restrict_m / k_mg_prolong_m).  DESIGN.md §10.
+// proper subset of the axes run kernels instantiated on that subset (k_mg_restrict_m / k_mg_prolong_m).  On a
+// distributed context the hierarchy lives on equal slabs of the slowest axis: mg_plan_slabs cuts mg_plan's levels where
+// the local slab extent stops being even, the level arrays carry one ghost plane per side, and the k_mg_*_s kernels run
+// with the context's ghost-plane exchange between them -- the one-rank cycle of the global grid, bit for bit.  DESIGN.md §10.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -238,6 +241,124 @@ __global__ __launch_bounds__(kBlock) void k_mg_prolong_m(MgLv Lf, MgLv Lc, int l
         x[i] = x[i] + mg_prolong_ax<MASK>(Lc, px, py, pz, e);
     }
 }
+// ------------------------------------------------------------------------------ slab forms (a distributed hierarchy)
+// The level's rows along the slowest axis are split over the ranks (equal slabs); every level array carries one ghost
+// plane before and after its interior, which the separate-launch exchange fills with the neighbours' boundary planes
+// (zero, as allocated, on the physical side of the first and last rank).  AX = the slab axis (1: y of a 2D grid,
+// 2: z of a 3D grid).  L holds the LOCAL extents.  Along AX the kernels read the ghost plane where the one-rank
+// kernels substitute 0 -- the same value -- and the transfers take their weights from the GLOBAL row and the GLOBAL
+// extents; only the memory row is local.  Per point the same expressions, fma order and final division as above.
+struct MgSl {
+    int ngf, ngc;  // global extents of the fine / coarse level along the slab axis
+    int of, oc;    // this rank's first global row (0-based) on the fine / coarse level
+};
+template <int AX>
+__device__ __forceinline__ double mg_off_s(const MgLv& L, const double* x, int i) {
+    const int ix = i % L.nx, t = i / L.nx, iy = t % L.ny;
+    const double xm = ix > 0 ? x[i - 1] : 0.0, xp = ix + 1 < L.nx ? x[i + 1] : 0.0;
+    double o = L.cx * (xm + xp);
+    if (AX == 1) {
+        const double ym = x[i - L.nx], yp = x[i + L.nx];
+        o = o + L.cy * (ym + yp);
+    } else {
+        if (L.ny > 1) {
+            const double ym = iy > 0 ? x[i - L.nx] : 0.0, yp = iy + 1 < L.ny ? x[i + L.nx] : 0.0;
+            o = o + L.cy * (ym + yp);
+        }
+        const int pl = L.nx * L.ny;
+        const double zm = x[i - pl], zp = x[i + pl];
+        o = o + L.cz * (zm + zp);
+    }
+    return o;
+}
+template <int AX>
+__device__ __forceinline__ double mg_sweep_pt_s(const MgLv& L, double omega, double om1, const double* x, const double* b,
+                                                const double* idg, int i) {
+    const double t = b[i] - mg_off_s<AX>(L, x, i);
+    return om1 * x[i] + omega * (idg[i] * t);
+}
+template <int AX>
+__device__ __forceinline__ double mg_restrict_pt_s(const MgLv& Lf, const MgLv& Lc, const MgSl& S, const double* r, int j) {
+    const int jx = j % Lc.nx, t = j / Lc.nx, jy = t % Lc.ny, jz = t / Lc.ny;
+    const MgAx ax = mg_rax(Lf.nx, Lc.nx, jx);
+    MgAx ay = AX == 1 ? mg_rax(S.ngf, S.ngc, S.oc + jy) : mg_rax(Lf.ny, Lc.ny, jy);
+    MgAx az = AX == 2 ? mg_rax(S.ngf, S.ngc, S.oc + jz) : mg_rax(Lf.nz, Lc.nz, jz);
+    MgAx& as = AX == 1 ? ay : az;
+    as.lo -= S.of;  // the memory row: -1 and the slab's extent are the ghost planes
+    // one ghost plane suffices for equal slabs (tests/test_hip_multigrid_dist.py checks it exhaustively); a row
+    // beyond it is never read
+    if (as.lo < -1 || as.lo + as.cnt - 1 > (AX == 1 ? Lf.ny : Lf.nz)) return NAN;
+    return mg_restrict_ax(Lf, ax, ay, az, r);
+}
+// mg_prolong_ax<7> with the coarse rows ylo <= jy < yhi and zlo <= jz < zhi in memory (the slab axis: -1 .. extent,
+// its ghost planes; the others 0 .. extent - 1 as there)
+__device__ __forceinline__ double mg_prolong_ax_s(const MgLv& Lc, const MgPx& px, const MgPx& py, const MgPx& pz, int ylo, int yhi,
+                                                  int zlo, int zhi, const double* e) {
+    double vz[2] = {0.0, 0.0};
+    for (int c = 0; c < 2; ++c) {
+        const int jz = pz.j - 1 + c;
+        double vy[2] = {0.0, 0.0};
+        for (int b = 0; b < 2; ++b) {
+            const int jy = py.j - 1 + b;
+            double lo = 0.0, hi = 0.0;
+            if (jz >= zlo && jz < zhi && jy >= ylo && jy < yhi) {
+                const int row = (jz * Lc.ny + jy) * Lc.nx;
+                if (px.j - 1 >= 0) lo = e[row + px.j - 1];
+                if (px.j < Lc.nx) hi = e[row + px.j];
+            }
+            vy[b] = (1.0 - px.w) * lo + px.w * hi;
+        }
+        vz[c] = (1.0 - py.w) * vy[0] + py.w * vy[1];
+    }
+    return (1.0 - pz.w) * vz[0] + pz.w * vz[1];
+}
+template <int AX>
+__device__ __forceinline__ double mg_prolong_pt_s(const MgLv& Lf, const MgLv& Lc, const MgSl& S, const double* e, int i) {
+    const int ix = i % Lf.nx, t = i / Lf.nx, iy = t % Lf.ny, iz = t / Lf.ny;
+    const MgPx px = mg_pax(Lf.nx, Lc.nx, ix);
+    MgPx py = AX == 1 ? mg_pax(S.ngf, S.ngc, S.of + iy) : mg_pax(Lf.ny, Lc.ny, iy);
+    MgPx pz = AX == 2 ? mg_pax(S.ngf, S.ngc, S.of + iz) : mg_pax(Lf.nz, Lc.nz, iz);
+    if (AX == 1) py.j -= S.oc;
+    else pz.j -= S.oc;
+    return mg_prolong_ax_s(Lc, px, py, pz, AX == 1 ? -1 : 0, AX == 1 ? Lc.ny + 1 : Lc.ny, AX == 2 ? -1 : 0,
+                           AX == 2 ? Lc.nz + 1 : Lc.nz, e);
+}
+
+template <int AX>
+__global__ __launch_bounds__(kBlock) void k_mg_sweep_s(MgLv L, double omega, double om1, double* xn, const double* __restrict__ x,
+                                                      const double* b, const double* __restrict__ idg) {
+    NK_CHUNKED(i, L.n) xn[i] = mg_sweep_pt_s<AX>(L, omega, om1, x, b, idg, (int)i);
+}
+template <int AX, bool RED>
+__global__ __launch_bounds__(kBlock) void k_mg_sweep_z_s(MgLv L, double omega, double om1, double sigma, double* z,
+                                                        const double* __restrict__ x, const double* b,
+                                                        const double* __restrict__ idg, double* __restrict__ part, int fin) {
+    __shared__ double sh[kShN];
+    double acc = 0.0;
+    NK_CHUNKED(i, L.n) {
+        const double bi = b[i];
+        const double zi = sigma * mg_sweep_pt_s<AX>(L, omega, om1, x, b, idg, (int)i);
+        z[i] = zi;
+        if (RED) acc = fma(bi, zi, acc);
+    }
+    if (RED) publish(acc, part, fin, sh);
+}
+template <int AX>
+__global__ __launch_bounds__(kBlock) void k_mg_resid_s(MgLv L, double* __restrict__ r, const double* __restrict__ x,
+                                                      const double* __restrict__ b, const double* __restrict__ dg) {
+    NK_CHUNKED(i, L.n) r[i] = b[i] - (mg_off_s<AX>(L, x, (int)i) + dg[i] * x[i]);
+}
+template <int AX>
+__global__ __launch_bounds__(kBlock) void k_mg_restrict_s(MgLv Lf, MgLv Lc, MgSl S, double* __restrict__ bc,
+                                                         const double* __restrict__ r) {
+    NK_CHUNKED(j, Lc.n) bc[j] = mg_restrict_pt_s<AX>(Lf, Lc, S, r, (int)j);
+}
+template <int AX>
+__global__ __launch_bounds__(kBlock) void k_mg_prolong_s(MgLv Lf, MgLv Lc, MgSl S, double* __restrict__ x,
+                                                        const double* __restrict__ e) {
+    NK_CHUNKED(i, Lf.n) x[i] = x[i] + mg_prolong_pt_s<AX>(Lf, Lc, S, e, (int)i);
+}
+
 // set-up: diag = dsum + s (dsum = Σ_a -2 c_a, summed in axis order on the host) and 1 / diag
 __global__ __launch_bounds__(kBlock) void k_mg_diag(int n, double dsum, const double* __restrict__ s, double* __restrict__ dg,
                                                    double* __restrict__ idg) {
@@ -411,6 +532,29 @@ int mg_plan_semi(const int64_t n0[3], const double h[3], const double k[3], doub
     return L;
 }
 
+// host: the plan of a slab-distributed grid in LOCAL extents (equal slabs of the slowest axis: every rank holds n0,
+// the global extent of that axis is nranks n0[ax]).  It is mg_plan of the global grid cut after L_d levels: level
+// l + 1 exists only while the local slab extent m_l is even, then m_{l+1} = m_l / 2 (the global nranks m_l >= 4 is
+// halved by mg_plan's rule as well; the other axes are whole on every rank).  *ax = the slab axis (1: y, 2: z).
+// Returns 0 with *why set where no distributed hierarchy exists.
+int mg_plan_slabs(const int64_t n0[3], int nranks, int max_levels, int64_t (*ext)[3], int* ax, const char** why) {
+    *why = nullptr;
+    *ax = n0[2] > 1 ? 2 : 1;
+    if (nranks < 2) *why = "a slab plan needs at least 2 ranks";
+    else if (n0[1] == 1 && n0[2] == 1) *why = "1D grids are not distributed (2D y-slabs and 3D z-slabs only)";
+    else if (n0[*ax] % 2 != 0) *why = "slabs of an odd number of planes cannot be coarsened";
+    else if ((int64_t)nranks * n0[*ax] >= ((int64_t)1 << 31)) *why = "at most 2^31 - 1 planes along the slab axis";
+    if (*why) return 0;
+    int64_t g[3] = {n0[0], n0[1], n0[2]};
+    g[*ax] *= nranks;
+    int Ld = 1;
+    for (int64_t ml = n0[*ax]; ml % 2 == 0; ml /= 2) ++Ld;
+    if (max_levels > 0) Ld = std::min(Ld, max_levels);
+    const int L = mg_plan(g, Ld, ext);  // (L == Ld: the global slab axis stays above 3 points while m_l is even)
+    for (int l = 0; l < L; ++l) ext[l][*ax] /= nranks;
+    return L;
+}
+
 }  // namespace
 }  // namespace nk
 
@@ -438,6 +582,10 @@ struct nk_mg {
            *dg[kMgMaxLevels] = {}, *idg[kMgMaxLevels] = {};
     double* part = nullptr;  // set-up: kMgMinmaxBlocks (min, max) pairs per level
     size_t tail_lds = 0;
+    // a distributed hierarchy (slabs of the slowest axis): lv holds the local extents
+    int slab_ax = 0;              // 0: one rank; 1 / 2: the slab axis (y of a 2D grid, z of a 3D grid)
+    int ng[kMgMaxLevels] = {};    // global extent of the level along the slab axis (nranks x the local one)
+    int64_t ghost[kMgMaxLevels] = {};  // doubles of the ghost plane before and after xa, xb, b, s (0: one rank)
 };
 
 namespace {
@@ -448,8 +596,31 @@ int mg_launch_sweep0(nk_mg* m, int l, double* x, const double* b) {
         hipLaunchKernelGGL(k_mg_sweep0, dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L.n, m->omega, x, b, m->idg[l]);
     });
 }
+// slabs: the ghost planes of level l's array x from the neighbour ranks (the context's separate-launch exchange)
+int mg_exchange(nk_mg* m, int l, const double* x) {
+    nk_problem lp = m->prob;
+    lp.nx = m->lv[l].nx;
+    lp.ny = m->lv[l].ny;
+    lp.nz = m->lv[l].nz;
+    return halo_exchange(m->c, &lp, x);
+}
+MgSl mg_slab(const nk_mg* m, int l) {
+    const int mf = m->slab_ax == 1 ? m->lv[l].ny : m->lv[l].nz, mc = m->slab_ax == 1 ? m->lv[l + 1].ny : m->lv[l + 1].nz;
+    return MgSl{m->ng[l], m->ng[l + 1], m->c->rank * mf, m->c->rank * mc};
+}
 int mg_launch_sweep(nk_mg* m, int l, double* xn, const double* x, const double* b) {
     const MgLv& L = m->lv[l];
+    if (m->slab_ax) {
+        NK_TRY(mg_exchange(m, l, x));
+        return launch(m->c, "mg_sweep", 32.0 * L.n, [&] {
+            if (m->slab_ax == 1)
+                hipLaunchKernelGGL(k_mg_sweep_s<1>, dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, m->omega,
+                                   1.0 - m->omega, xn, x, b, m->idg[l]);
+            else
+                hipLaunchKernelGGL(k_mg_sweep_s<2>, dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, m->omega,
+                                   1.0 - m->omega, xn, x, b, m->idg[l]);
+        });
+    }
     return launch(m->c, "mg_sweep", 32.0 * L.n, [&] {
         hipLaunchKernelGGL(k_mg_sweep, dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, m->omega, 1.0 - m->omega, xn, x, b,
                            m->idg[l]);
@@ -471,8 +642,23 @@ int mg_launch_sweep_z(nk_mg* m, double* z, const double* x, const double* b, con
     int fin = 0;
     double* part = o.red ? red_out(c, g, o.red, &fin) : nullptr;
     const char* name = x ? (o.red ? "mg_sweep_dot" : "mg_sweep") : (o.red ? "mg_sweep0_dot" : "mg_sweep0");
+    if (x && m->slab_ax) NK_TRY(mg_exchange(m, 0, x));
     return launch(c, name, (x ? 32.0 : 24.0) * L.n, [&] {
-        if (x && o.red)
+        if (x && m->slab_ax) {
+            const double om = m->omega, om1 = 1.0 - m->omega;
+            if (m->slab_ax == 1 && o.red)
+                hipLaunchKernelGGL((k_mg_sweep_z_s<1, true>), dim3(g), dim3(kBlock), 0, c->stream, L, om, om1, o.sigma, z, x, b,
+                                   m->idg[0], part, fin);
+            else if (m->slab_ax == 1)
+                hipLaunchKernelGGL((k_mg_sweep_z_s<1, false>), dim3(g), dim3(kBlock), 0, c->stream, L, om, om1, o.sigma, z, x, b,
+                                   m->idg[0], part, fin);
+            else if (o.red)
+                hipLaunchKernelGGL((k_mg_sweep_z_s<2, true>), dim3(g), dim3(kBlock), 0, c->stream, L, om, om1, o.sigma, z, x, b,
+                                   m->idg[0], part, fin);
+            else
+                hipLaunchKernelGGL((k_mg_sweep_z_s<2, false>), dim3(g), dim3(kBlock), 0, c->stream, L, om, om1, o.sigma, z, x, b,
+                                   m->idg[0], part, fin);
+        } else if (x && o.red)
             hipLaunchKernelGGL(k_mg_sweep_z<true>, dim3(g), dim3(kBlock), 0, c->stream, L, m->omega, 1.0 - m->omega, o.sigma, z, x, b,
                                m->idg[0], part, fin);
         else if (x)
@@ -567,6 +753,16 @@ void mg_prolong_m(nk_mg* m, const MgLv& Lf, const MgLv& Lc, bool s32, double* x,
 // setup: the restriction of s during set-up (a profiler class of its own)
 int mg_restrict(nk_mg* m, int l, double* bc, const double* r, bool setup) {
     const MgLv &Lf = m->lv[l], &Lc = m->lv[l + 1];
+    if (m->slab_ax) {  // slabs: r's ghost planes first, then the slab form of the general kernel
+        NK_TRY(mg_exchange(m, l, r));
+        const MgSl S = mg_slab(m, l);
+        return launch(m->c, (setup ? kMgSetupName : kMgRestrictName)[0], 8.0 * Lf.n + 8.0 * Lc.n, [&] {
+            if (m->slab_ax == 1)
+                hipLaunchKernelGGL(k_mg_restrict_s<1>, dim3(wide_blocks(Lc.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, S, bc, r);
+            else
+                hipLaunchKernelGGL(k_mg_restrict_s<2>, dim3(wide_blocks(Lc.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, S, bc, r);
+        });
+    }
     const MgXfer t = mg_xfer(m, l);
     return launch(m->c, (setup ? kMgSetupName : kMgRestrictName)[t.mask], 8.0 * Lf.n + 8.0 * Lc.n, [&] {
         switch (t.general ? 0 : t.mask) {
@@ -582,6 +778,16 @@ int mg_restrict(nk_mg* m, int l, double* bc, const double* r, bool setup) {
 }
 int mg_prolong(nk_mg* m, int l, double* x, const double* e) {
     const MgLv &Lf = m->lv[l], &Lc = m->lv[l + 1];
+    if (m->slab_ax) {  // slabs: the coarse e's ghost planes first
+        NK_TRY(mg_exchange(m, l + 1, e));
+        const MgSl S = mg_slab(m, l);
+        return launch(m->c, kMgProlongName[0], 16.0 * Lf.n + 8.0 * Lc.n, [&] {
+            if (m->slab_ax == 1)
+                hipLaunchKernelGGL(k_mg_prolong_s<1>, dim3(wide_blocks(Lf.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, S, x, e);
+            else
+                hipLaunchKernelGGL(k_mg_prolong_s<2>, dim3(wide_blocks(Lf.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, S, x, e);
+        });
+    }
     const MgXfer t = mg_xfer(m, l);
     return launch(m->c, kMgProlongName[t.mask], 16.0 * Lf.n + 8.0 * Lc.n, [&] {
         switch (t.general ? 0 : t.mask) {
@@ -597,9 +803,12 @@ int mg_prolong(nk_mg* m, int l, double* x, const double* e) {
 }
 
 int mg_free(nk_mg* m) {
-    for (int l = 0; l < kMgMaxLevels; ++l)
-        for (double* q : {m->xa[l], m->xb[l], m->b[l], m->s[l], m->dg[l], m->idg[l]})
+    for (int l = 0; l < kMgMaxLevels; ++l) {
+        for (double* q : {m->xa[l], m->xb[l], m->b[l], m->s[l]})
+            if (q) (void)hipFree(q - m->ghost[l]);
+        for (double* q : {m->dg[l], m->idg[l]})
             if (q) (void)hipFree(q);
+    }
     if (m->part) (void)hipFree(m->part);
     delete m;
     return NK_OK;
@@ -607,13 +816,39 @@ int mg_free(nk_mg* m) {
 
 bool mg_kind_ok(int kind) { return (kind >= NK_BRATU1D && kind <= NK_HEAT3D_TRAPEZOID) || kind == NK_BRATU3D; }
 
+// slabs: pos[l] / neg[l] of this rank's rows -> of the whole level, through the context's cross-rank sum.  Every rank
+// adds 1 (positive) + 64 (negative) per level (at most kMbRanks = 32 < 64 ranks: no carry), four levels of 12 bits to
+// a scalar (exact in a double); a level is positive / negative when the count is nranks.  One host sync per scalar.
+int mg_agree(nk_mg* m, bool* pos, bool* neg) {
+    nk_ctx* c = m->c;
+    for (int l0 = 0; l0 < m->nlev_alloc; l0 += 4) {
+        double code = 0.0, f = 1.0;
+        for (int l = l0; l < l0 + 4 && l < m->nlev_alloc; ++l, f *= 4096.0) code += f * ((pos[l] ? 1.0 : 0.0) + (neg[l] ? 64.0 : 0.0));
+        Red r{};
+        int fin = 0;
+        double* part = red_out(c, 1, &r, &fin);
+        r.fin = nullptr;  // nothing was folded: the one partial is the value
+        c->hpin[1] = code;
+        NK_HIP(c, hipMemcpyAsync(part, c->hpin + 1, sizeof(double), hipMemcpyHostToDevice, c->stream));
+        double sum = 0.0;
+        NK_TRY(host_scalar(c, r, 0, &sum));
+        int64_t S = (int64_t)sum;
+        for (int l = l0; l < l0 + 4 && l < m->nlev_alloc; ++l, S /= 4096) {
+            pos[l] = (S % 64) == c->nranks;
+            neg[l] = ((S / 64) % 64) == c->nranks;
+        }
+    }
+    return NK_OK;
+}
+
 // diag and 1 / diag of every level from k and s_0 (already in m->s[0]); level 0's from nk_jacobian_diag when
 // `jac` (bit-identical to J's own diagonal); then the sign check that may truncate the hierarchy
 int mg_setup(nk_mg* m, const double k[3], const nk_problem* jac, const double* u) {
     nk_ctx* c = m->c;
     for (int l = 0; l < m->nlev_alloc; ++l) {
         MgLv& L = m->lv[l];
-        const int ext[3] = {L.nx, L.ny, L.nz};
+        int ext[3] = {L.nx, L.ny, L.nz};
+        if (m->slab_ax) ext[m->slab_ax] = m->ng[l];  // the spacing of the global grid
         double cc[3] = {0.0, 0.0, 0.0}, dsum = 0.0;
         for (int a = 0; a < m->dim; ++a) {
             const double h = l == 0 ? m->h0[a] : m->len[a] / (double)(ext[a] + 1);
@@ -639,19 +874,29 @@ int mg_setup(nk_mg* m, const double k[3], const nk_problem* jac, const double* u
     std::vector<double> part((size_t)2 * kMgMinmaxBlocks * m->nlev_alloc);
     NK_HIP(c, hipMemcpyAsync(part.data(), m->part, part.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     NK_HIP(c, hipStreamSynchronize(c->stream));
+    // per level: the whole diagonal is positive / negative (and finite)
+    bool pos[kMgMaxLevels], neg[kMgMaxLevels];
+    for (int l = 0; l < m->nlev_alloc; ++l) {
+        const int g = std::min(kMgMinmaxBlocks, wide_blocks(m->lv[l].n));
+        double lo = INFINITY, hi = -INFINITY;
+        for (int b = 0; b < g; ++b) {
+            lo = std::fmin(lo, part[(size_t)2 * (kMgMinmaxBlocks * l + b)]);
+            hi = std::fmax(hi, part[(size_t)2 * (kMgMinmaxBlocks * l + b) + 1]);
+        }
+        const bool finite = !(std::isinf(lo) || std::isinf(hi));
+        pos[l] = finite && lo > 0.0;
+        neg[l] = finite && hi < 0.0;
+    }
+    // slabs: of the whole level, not of this rank's rows -- every rank must keep the same levels (and sigma), or the
+    // ranks that keep more wait in their exchanges for one that never arrives
+    if (m->slab_ax) NK_TRY(mg_agree(m, pos, neg));
     int ok = 0, ok_spd = 0;
     bool neg0 = false;
     for (; ok < m->nlev_alloc; ++ok) {
-        const int g = std::min(kMgMinmaxBlocks, wide_blocks(m->lv[ok].n));
-        double lo = INFINITY, hi = -INFINITY;
-        for (int b = 0; b < g; ++b) {
-            lo = std::fmin(lo, part[(size_t)2 * (kMgMinmaxBlocks * ok + b)]);
-            hi = std::fmax(hi, part[(size_t)2 * (kMgMinmaxBlocks * ok + b) + 1]);
-        }
-        if (!(lo > 0.0 || hi < 0.0) || std::isinf(lo) || std::isinf(hi)) break;
+        if (!(pos[ok] || neg[ok])) break;
         // the SPD form's hierarchy: the leading levels whose diagonal has level 0's sign (a mixed one is not definite)
-        if (ok == 0) neg0 = hi < 0.0;
-        if (ok_spd == ok && (hi < 0.0) == neg0) ok_spd = ok + 1;
+        if (ok == 0) neg0 = neg[0];
+        if (ok_spd == ok && neg[ok] == neg0) ok_spd = ok + 1;
     }
     m->ready = false;
     if (ok == 0) return fail(c, NK_E_ARG, "multigrid: the diagonal of the operator changes sign, vanishes or is not finite");
@@ -670,6 +915,22 @@ int nk_mg_plan(const int64_t n[3], int32_t max_levels, int64_t* extents, int32_t
     if (!n || !nlevels || n[0] < 1 || n[1] < 1 || n[2] < 1 || max_levels < 0 || cap < 0 || (cap > 0 && !extents)) return NK_E_ARG;
     int64_t ext[kMgMaxLevels][3];
     const int L = mg_plan(n, max_levels, ext);
+    for (int l = 0; l < L && l < cap; ++l)
+        for (int a = 0; a < 3; ++a) extents[3 * l + a] = ext[l][a];
+    *nlevels = L;
+    return NK_OK;
+}
+
+int nk_mg_plan_slabs(const int64_t n_local[3], int32_t nranks, int32_t max_levels, int64_t* extents, int32_t cap,
+                     int32_t* nlevels) {
+    if (!n_local || !nlevels || n_local[0] < 1 || n_local[1] < 1 || n_local[2] < 1 || max_levels < 0 || cap < 0 ||
+        (cap > 0 && !extents))
+        return NK_E_ARG;
+    int64_t ext[kMgMaxLevels][3];
+    int ax = 0;
+    const char* why = nullptr;
+    const int L = mg_plan_slabs(n_local, nranks, max_levels, ext, &ax, &why);
+    if (L == 0) return NK_E_ARG;
     for (int l = 0; l < L && l < cap; ++l)
         for (int a = 0; a < 3; ++a) extents[3 * l + a] = ext[l][a];
     *nlevels = L;
@@ -706,7 +967,17 @@ int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int6
         return fail(c, NK_E_ARG, "multigrid: built-in stencil kinds only (a user residual's coefficients are unknown; "
                                  "give them with nk_mg_set_operator on a built-in kind's grid)");
     if (p->bc != NK_BC_ZERO) return fail(c, NK_E_ARG, "multigrid: bc_zero! only (periodic boundaries are not implemented)");
-    if (c->nranks != 1) return fail(c, NK_E_ARG, "multigrid: one rank only (a distributed context is not implemented)");
+    // a distributed context: equal slabs of the slowest axis.  Every refusal depends on values all
+    // ranks hold alike (kind, bc, process grid, local extents -- equal by precondition -- and options), and comes
+    // before the first exchange is enqueued
+    const bool dist = c->nranks != 1;
+    if (dist && (c->px * c->py > 1 || block_self(c)))
+        return fail(c, NK_E_ARG, "multigrid: slabs only on a distributed context (3D blocks are not implemented)");
+    if (dist && p->kind == NK_BRATU1D) return fail(c, NK_E_ARG, "multigrid: 1D kinds are not implemented on a distributed context");
+    if (dist && p->kind == NK_BRATU3D)
+        return fail(c, NK_E_ARG, "multigrid: NK_BRATU3D runs on one rank (a distributed context is not implemented for it)");
+    if (dist && given)
+        return fail(c, NK_E_ARG, "multigrid: a level list (semicoarsening) is not implemented on a distributed context");
     Geo g;
     NK_TRY(geometry(c, p, &g));
     if (g.n >= ((int64_t)1 << 31)) return fail(c, NK_E_ARG, "multigrid: at most 2^31 - 1 points");
@@ -717,7 +988,7 @@ int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int6
     const int64_t n0[3] = {p->nx, p->ny, p->nz};
     const double h[3] = {p->hx, p->hy, p->hz};
     int64_t ext[kMgMaxLevels][3];
-    int nlev = 0;
+    int nlev = 0, slab_ax = 0;
     if (given) {
         if (nlevels < 1 || nlevels > kMgMaxLevels) return fail(c, NK_E_ARG, "multigrid: the level list has fewer than 1 or more than 32 levels");
         for (int a = 0; a < 3; ++a)
@@ -739,6 +1010,10 @@ int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int6
                 return fail(c, NK_E_ARG, "multigrid: level " + std::to_string(l) + " of the level list coarsens no axis");
         }
         nlev = nlevels;
+    } else if (dist) {
+        const char* why = nullptr;
+        nlev = mg_plan_slabs(n0, c->nranks, opts ? opts->max_levels : 0, ext, &slab_ax, &why);
+        if (nlev == 0) return fail(c, NK_E_ARG, std::string("multigrid on a distributed context: ") + why);
     } else {
         nlev = mg_plan(n0, opts ? opts->max_levels : 0, ext);
     }
@@ -750,9 +1025,11 @@ int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int6
     m->cs = cs;
     m->omega = omega;
     m->nlev_alloc = nlev;
+    m->slab_ax = slab_ax;
     for (int a = 0; a < 3; ++a) {
         m->h0[a] = h[a];
-        m->len[a] = (double)(n0[a] + 1) * h[a];
+        // slabs: the length of the global grid along the slab axis, as the one-rank hierarchy of that grid has it
+        m->len[a] = (double)((a == slab_ax && dist ? c->nranks * n0[a] : n0[a]) + 1) * h[a];
     }
     m->tail = m->nlev_alloc;
     for (int l = 0; l < m->nlev_alloc; ++l) {
@@ -760,11 +1037,29 @@ int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int6
         L.nx = (int)ext[l][0]; L.ny = (int)ext[l][1]; L.nz = (int)ext[l][2];
         L.n = L.nx * L.ny * L.nz;
         L.cx = L.cy = L.cz = 0.0;
-        if (m->tail == m->nlev_alloc && L.n <= kMgTailPoints && m->nlev_alloc - l <= kMgTailLevels) m->tail = l;
+        // (a distributed hierarchy has no tail: every level runs the per-level kernels, with exchanges between them)
+        if (!dist && m->tail == m->nlev_alloc && L.n <= kMgTailPoints && m->nlev_alloc - l <= kMgTailLevels) m->tail = l;
         const size_t bytes = sizeof(double) * (size_t)L.n;
         bool ok = true;
-        for (double** q : {&m->xa[l], &m->xb[l], &m->s[l], &m->dg[l], &m->idg[l]}) ok = ok && hipMalloc(q, bytes) == hipSuccess;
-        if (l > 0) ok = ok && hipMalloc(&m->b[l], bytes) == hipSuccess;
+        // slabs: xa, xb, s, b carry one ghost plane before and after the interior, zero from here on where no
+        // neighbour writes it (the physical side of the first and last rank: the Dirichlet boundary)
+        const int64_t gh = dist ? (int64_t)L.nx * (slab_ax == 2 ? L.ny : 1) : 0;
+        if (dist) m->ng[l] = (int)(c->nranks * ext[l][slab_ax]);
+        m->ghost[l] = gh;
+        auto with_ghosts = [&](double** q) {
+            double* base = nullptr;
+            const size_t all = bytes + 2 * sizeof(double) * (size_t)gh;
+            if (hipMalloc(&base, all) != hipSuccess) return false;
+            if (gh && hipMemsetAsync(base, 0, all, c->stream) != hipSuccess) {
+                (void)hipFree(base);
+                return false;
+            }
+            *q = base + gh;
+            return true;
+        };
+        for (double** q : {&m->xa[l], &m->xb[l], &m->s[l]}) ok = ok && with_ghosts(q);
+        for (double** q : {&m->dg[l], &m->idg[l]}) ok = ok && hipMalloc(q, bytes) == hipSuccess;
+        if (l > 0) ok = ok && with_ghosts(&m->b[l]);
         if (!ok) {
             (void)hipGetLastError();
             mg_free(m);
@@ -903,8 +1198,14 @@ int nk::mg_apply_red(nk_mg* m, double* z, const double* v, Red* red) {
         NK_TRY(mg_sweeps(m, l, b, 0, m->nu, &cur[l], nullptr, out));
         double* r = cur[l] == m->xa[l] ? m->xb[l] : m->xa[l];
         const MgLv& Lv = m->lv[l];
+        if (m->slab_ax) NK_TRY(mg_exchange(m, l, cur[l]));
         NK_TRY(launch(c, "mg_resid", 32.0 * Lv.n, [&] {
-            hipLaunchKernelGGL(k_mg_resid, dim3(wide_blocks(Lv.n)), dim3(kBlock), 0, c->stream, Lv, r, cur[l], b, m->dg[l]);
+            if (m->slab_ax == 1)
+                hipLaunchKernelGGL(k_mg_resid_s<1>, dim3(wide_blocks(Lv.n)), dim3(kBlock), 0, c->stream, Lv, r, cur[l], b, m->dg[l]);
+            else if (m->slab_ax == 2)
+                hipLaunchKernelGGL(k_mg_resid_s<2>, dim3(wide_blocks(Lv.n)), dim3(kBlock), 0, c->stream, Lv, r, cur[l], b, m->dg[l]);
+            else
+                hipLaunchKernelGGL(k_mg_resid, dim3(wide_blocks(Lv.n)), dim3(kBlock), 0, c->stream, Lv, r, cur[l], b, m->dg[l]);
         }));
         NK_TRY(mg_restrict(m, l, m->b[l + 1], r, false));
     }

@@ -445,7 +445,8 @@ HipGmresPreconditioner(J::Ariadne.JacobianOperator, itmax::Integer) =
 nkprecond(P::HipGmresPreconditioner) = NkPrecond(NK_PRECOND_GMRES, C_NULL, C_NULL, C_NULL, P.ws.ptr, P.itmax)
 
 # Geometric multigrid V-cycle for the stencil Jacobians (NK_PRECOND_MG, nkhip.h): built-in residuals,
-# bc_zero!, one rank.  `N = hip_multigrid` is a factory: one hierarchy per (context, grid, kind), refreshed
+# bc_zero!, one rank (on a distributed context nk_mg_create builds the slab-distributed hierarchy: equal slabs, see
+# nkhip.h and mg_plan_slabs).  `N = hip_multigrid` is a factory: one hierarchy per (context, grid, kind), refreshed
 # from each Newton step's u (nk_mg_set_jacobian).  Valid for :gmres and :fgmres, as N or M; and in its SPD form
 # (`spd = true` / mg_set_spd!: z = σ V(v), σ the sign of the level-0 diagonal) as M of :cg -- `M = hip_multigrid_spd`.
 const NK_PRECOND_MG = Int32(5)
@@ -530,6 +531,17 @@ function mg_plan(n::NTuple{3, Int64}; max_levels = 0)
     rc = ccall((:nk_mg_plan, libnkhip), Cint, (Ref{NTuple{3, Int64}}, Int32, Ptr{Int64}, Int32, Ref{Int32}),
                Ref(n), max_levels, ext, 64, nl)
     rc == 0 || error("nk_mg_plan: invalid argument")
+    return [Tuple(ext[3l + 1:3l + 3]) for l in 0:nl[] - 1]
+end
+# the plan of a slab-distributed hierarchy in local extents (host only): n = one rank's extents (equal slabs of the
+# slowest axis); level l + 1 exists only while the local slab extent is even.  On a distributed context
+# HipMultigridPreconditioner builds that hierarchy (nk_mg_create, nkhip.h)
+function mg_plan_slabs(n::NTuple{3, Int64}, nranks::Integer; max_levels = 0)
+    ext = Vector{Int64}(undef, 3 * 64)
+    nl = Ref{Int32}(0)
+    rc = ccall((:nk_mg_plan_slabs, libnkhip), Cint, (Ref{NTuple{3, Int64}}, Int32, Int32, Ptr{Int64}, Int32, Ref{Int32}),
+               Ref(n), nranks, max_levels, ext, 64, nl)
+    rc == 0 || error("nk_mg_plan_slabs: no slab plan (a 1D grid, an odd local slab extent, fewer than 2 ranks)")
     return [Tuple(ext[3l + 1:3l + 3]) for l in 0:nl[] - 1]
 end
 # the semicoarsened plan (host only): only the axes with c_a = |k_a| / h_a² >= threshold * max c are halved
