@@ -9,8 +9,12 @@
 // grids and coefficients), nk_mg_create_levels takes any such list; the transfers between two levels that coarsen a
 // proper subset of the axes run kernels instantiated on that subset (k_mg_restrict_m / k_mg_prolong_m).  On a
 // distributed context the hierarchy lives on equal slabs of the slowest axis: mg_plan_slabs cuts mg_plan's levels where
-// the local slab extent stops being even, the level arrays carry one ghost plane per side, and the k_mg_*_s kernels run
-// with the context's ghost-plane exchange between them -- the one-rank cycle of the global grid, bit for bit.  DESIGN.md §10.
+// the local slab extent stops being even, the level arrays carry one ghost plane per side, and the same kernels run in
+// their slab instantiation (AX = the slab axis; 0: one rank) with the context's ghost-plane exchange between them --
+// the one-rank cycle of the global grid, bit for bit.  One text per expression: the device functions and the per-level
+// kernels are templates on AX, and mg_pick turns the runtime AX, RED, MASK, S32 and OUT into the instantiation a
+// launcher runs.  The host-only rules (plans, level-list validation, kernel choice, grids, the tail's extent, the
+// transfers' integer weights) are nk_mg_plan.hpp, which a CPU test calls.  DESIGN.md §10.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,35 +24,40 @@
 #include <vector>
 
 #include "nk_device.hpp"
+#include "nk_mg_plan.hpp"
 
 namespace nk {
 namespace {
-
-constexpr int kMgMaxLevels = 32;
-constexpr int kMgTailLevels = 12;      // 1024 -> 2 points in 1D is 10 levels
-constexpr int kMgTailPoints = 1024;    // first tail level: at most this many points (5 arrays x < 2 x 1024 x 8 B = 80 KiB LDS)
-constexpr int kMgTailThreads = 1024;
-// LDS of the tail: its levels at least halve, so they hold at most 2 kMgTailPoints - 1 points, five arrays each
-constexpr size_t kMgTailLds = 5 * sizeof(double) * (2 * kMgTailPoints - 1);
-constexpr int kMgMinmaxBlocks = 64;
 
 struct MgLv {
     int nx, ny, nz, n;
     double cx, cy, cz;  // k_a / h_a^2 (0 along an unused axis)
 };
+// A distributed hierarchy: the level's rows along the slowest axis are split over the ranks (equal slabs); every level
+// array carries one ghost plane before and after its interior, which the separate-launch exchange fills with the
+// neighbours' boundary planes (zero, as allocated, on the physical side of the first and last rank).  AX = the slab
+// axis (1: y of a 2D grid, 2: z of a 3D grid; 0: one rank).  L holds the LOCAL extents.  Along AX the device functions
+// read the ghost plane where the one-rank form substitutes 0 -- the same value -- and the transfers take their weights
+// from the GLOBAL row and the GLOBAL extents; only the memory row is local.
+struct MgSl {
+    int ngf, ngc;  // global extents of the fine / coarse level along the slab axis
+    int of, oc;    // this rank's first global row (0-based) on the fine / coarse level
+};
 
-// Σ_a c_a (x_- + x_+) at point i, zero Dirichlet boundary
+// Σ_a c_a (x_- + x_+) at point i, zero Dirichlet boundary.  Along AX the neighbours are the ghost planes, read as they
+// are (the local extent along AX may be 1); a y-slab grid is 2D
+template <int AX = 0>
 __device__ __forceinline__ double mg_off(const MgLv& L, const double* x, int i) {
     const int ix = i % L.nx, t = i / L.nx, iy = t % L.ny, iz = t / L.ny;
     const double xm = ix > 0 ? x[i - 1] : 0.0, xp = ix + 1 < L.nx ? x[i + 1] : 0.0;
     double o = L.cx * (xm + xp);
-    if (L.ny > 1) {
-        const double ym = iy > 0 ? x[i - L.nx] : 0.0, yp = iy + 1 < L.ny ? x[i + L.nx] : 0.0;
+    if (AX == 1 || L.ny > 1) {
+        const double ym = AX == 1 || iy > 0 ? x[i - L.nx] : 0.0, yp = AX == 1 || iy + 1 < L.ny ? x[i + L.nx] : 0.0;
         o = o + L.cy * (ym + yp);
     }
-    if (L.nz > 1) {
+    if (AX == 2 || (AX == 0 && L.nz > 1)) {
         const int pl = L.nx * L.ny;
-        const double zm = iz > 0 ? x[i - pl] : 0.0, zp = iz + 1 < L.nz ? x[i + pl] : 0.0;
+        const double zm = AX == 2 || iz > 0 ? x[i - pl] : 0.0, zp = AX == 2 || iz + 1 < L.nz ? x[i + pl] : 0.0;
         o = o + L.cz * (zm + zp);
     }
     return o;
@@ -58,42 +67,18 @@ __device__ __forceinline__ double mg_off(const MgLv& L, const double* x, int i) 
 __device__ __forceinline__ double mg_sweep0_pt(double omega, const double* b, const double* idg, int i) {
     return omega * (idg[i] * b[i]);
 }
+template <int AX = 0>
 __device__ __forceinline__ double mg_sweep_pt(const MgLv& L, double omega, double om1, const double* x, const double* b,
                                               const double* idg, int i) {
-    const double t = b[i] - mg_off(L, x, i);
+    const double t = b[i] - mg_off<AX>(L, x, i);
     return om1 * x[i] + omega * (idg[i] * t);
 }
+template <int AX = 0>
 __device__ __forceinline__ double mg_resid_pt(const MgLv& L, const double* x, const double* b, const double* dg, int i) {
-    return b[i] - (mg_off(L, x, i) + dg[i] * x[i]);
+    return b[i] - (mg_off<AX>(L, x, i) + dg[i] * x[i]);
 }
 
-// one axis of R = D^-1 P^T for coarse point j (0-based): the fine points lo .. lo + cnt - 1 with integer weights
-// w = (n_f + 1) - |I (n_c + 1) - J (n_f + 1)| (I, J 1-based) and their sum D; an axis that was not coarsened is
-// the identity
-struct MgAx {
-    int lo, cnt, w[4], D;
-};
-// I: the integer type of the products, which reach n_f^2 / 2: 64-bit in general (an axis may have more than 65534
-// points), 32-bit where the launcher has checked that they fit (the same integers either way)
-template <typename I>
-__device__ __forceinline__ MgAx mg_rax_t(int nf, int nc, int j) {
-    MgAx a{j, 1, {1, 0, 0, 0}, 1};
-    if (nf == nc) return a;
-    const I J = j + 1, F = nf + 1, Cc = nc + 1;
-    I lo = ((J - 1) * F) / Cc + 1, hi = ((J + 1) * F - 1) / Cc;
-    lo = lo < 1 ? 1 : lo;
-    hi = hi > nf ? nf : hi;
-    hi = hi > lo + 3 ? lo + 3 : hi;  // the open interval has length 2 (n_f + 1) / (n_c + 1) <= 4: at most 4 points
-    a.lo = (int)(lo - 1);
-    a.cnt = (int)(hi - lo + 1);
-    a.D = 0;
-    for (int t = 0; t < 4; ++t) {
-        const I d = (lo + t) * Cc - J * F;
-        a.w[t] = t < a.cnt ? (int)(F - (d < 0 ? -d : d)) : 0;
-        a.D += a.w[t];
-    }
-    return a;
-}
+// the transfers' weights along one axis: mg_rax_t / mg_pax_t of nk_mg_plan.hpp, here with 64-bit products
 __device__ __forceinline__ MgAx mg_rax(int nf, int nc, int j) { return mg_rax_t<int64_t>(nf, nc, j); }
 // the gather of one coarse point from its three axes, and the final division
 __device__ __forceinline__ double mg_restrict_ax(const MgLv& Lf, const MgAx& ax, const MgAx& ay, const MgAx& az, const double* r) {
@@ -106,30 +91,34 @@ __device__ __forceinline__ double mg_restrict_ax(const MgLv& Lf, const MgAx& ax,
         }
     return acc / ((double)az.D * (double)ay.D * (double)ax.D);
 }
-__device__ __forceinline__ double mg_restrict_pt(const MgLv& Lf, const MgLv& Lc, const double* r, int j) {
+// slabs: the weights along AX come from the global row and extents, then lo shifts to the memory row (-1 and the
+// slab's extent are the ghost planes)
+template <int AX = 0>
+__device__ __forceinline__ double mg_restrict_pt(const MgLv& Lf, const MgLv& Lc, const double* r, int j, const MgSl& S = MgSl{}) {
     const int jx = j % Lc.nx, t = j / Lc.nx, jy = t % Lc.ny, jz = t / Lc.ny;
-    return mg_restrict_ax(Lf, mg_rax(Lf.nx, Lc.nx, jx), mg_rax(Lf.ny, Lc.ny, jy), mg_rax(Lf.nz, Lc.nz, jz), r);
+    const MgAx ax = mg_rax(Lf.nx, Lc.nx, jx);
+    MgAx ay = AX == 1 ? mg_rax(S.ngf, S.ngc, S.oc + jy) : mg_rax(Lf.ny, Lc.ny, jy);
+    MgAx az = AX == 2 ? mg_rax(S.ngf, S.ngc, S.oc + jz) : mg_rax(Lf.nz, Lc.nz, jz);
+    if constexpr (AX != 0) {
+        MgAx& as = AX == 1 ? ay : az;
+        as.lo -= S.of;
+        // one ghost plane suffices for equal slabs (tests/test_mg_plan.py checks it exhaustively); a row beyond it
+        // is never read
+        if (as.lo < -1 || as.lo + as.cnt - 1 > (AX == 1 ? Lf.ny : Lf.nz)) return NAN;
+    }
+    return mg_restrict_ax(Lf, ax, ay, az, r);
 }
 
-// one axis of P for fine point i (0-based): coarse points j - 1 and j (0-based; outside 0 .. n_c - 1: the
-// boundary, 0) with weights 1 - w and w, w = (q mod (n_f + 1)) / (n_f + 1), q = (i + 1) (n_c + 1), j = q / (n_f + 1)
-struct MgPx {
-    int j;
-    double w;
-};
-template <typename I>
-__device__ __forceinline__ MgPx mg_pax_t(int nf, int nc, int i) {
-    if (nf == nc) return MgPx{i + 1, 0.0};
-    const I q = (I)(i + 1) * (nc + 1), F = nf + 1;  // q reaches n_f^2 / 2 (I as in mg_rax_t)
-    return MgPx{(int)(q / F), (double)(q % F) / (double)F};
-}
 __device__ __forceinline__ MgPx mg_pax(int nf, int nc, int i) { return mg_pax_t<int64_t>(nf, nc, i); }
 // the interpolation of one fine point from its three axes.  MASK (bit a: axis a is coarsened) = 7 is the general form,
 // in which an axis that was not coarsened is the identity through its weights 1 and 0; an axis outside MASK is known
 // to be the identity, and its zero-weight neighbour is neither read nor added: the same value (a term 0 * e of a
-// finite e only decides the sign of a zero result)
-template <int MASK>
-__device__ __forceinline__ double mg_prolong_ax(const MgLv& Lc, const MgPx& px, const MgPx& py, const MgPx& pz, const double* e) {
+// finite e only decides the sign of a zero result).  The coarse rows in memory are 0 .. extent - 1, and -1 .. extent
+// along the slab axis AX (its ghost planes).  A slab form takes the four bounds by value (mg_prolong_pt), the one-rank
+// form reads the level's extents in place: the other way round either kernel compiles to some 25 instructions more
+template <int MASK, int AX = 0>
+__device__ __forceinline__ double mg_prolong_ax(const MgLv& Lc, const MgPx& px, const MgPx& py, const MgPx& pz, const double* e,
+                                                int ylo = 0, int yhi = 0, int zlo = 0, int zhi = 0) {
     constexpr bool CX = (MASK & 1) != 0, CY = (MASK & 2) != 0, CZ = (MASK & 4) != 0;
     double vz[2] = {0.0, 0.0};
     for (int c = 0; c < (CZ ? 2 : 1); ++c) {
@@ -138,7 +127,7 @@ __device__ __forceinline__ double mg_prolong_ax(const MgLv& Lc, const MgPx& px, 
         for (int b = 0; b < (CY ? 2 : 1); ++b) {
             const int jy = py.j - 1 + b;
             double lo = 0.0, hi = 0.0;
-            if (jz >= 0 && jz < Lc.nz && jy >= 0 && jy < Lc.ny) {
+            if (AX == 0 ? jz >= 0 && jz < Lc.nz && jy >= 0 && jy < Lc.ny : jz >= zlo && jz < zhi && jy >= ylo && jy < yhi) {
                 const int row = (jz * Lc.ny + jy) * Lc.nx;
                 if (px.j - 1 >= 0) lo = e[row + px.j - 1];
                 if (CX && px.j < Lc.nx) hi = e[row + px.j];
@@ -149,20 +138,28 @@ __device__ __forceinline__ double mg_prolong_ax(const MgLv& Lc, const MgPx& px, 
     }
     return CZ ? (1.0 - pz.w) * vz[0] + pz.w * vz[1] : vz[0];
 }
-__device__ __forceinline__ double mg_prolong_pt(const MgLv& Lf, const MgLv& Lc, const double* e, int i) {
+template <int AX = 0>
+__device__ __forceinline__ double mg_prolong_pt(const MgLv& Lf, const MgLv& Lc, const double* e, int i, const MgSl& S = MgSl{}) {
     const int ix = i % Lf.nx, t = i / Lf.nx, iy = t % Lf.ny, iz = t / Lf.ny;
-    return mg_prolong_ax<7>(Lc, mg_pax(Lf.nx, Lc.nx, ix), mg_pax(Lf.ny, Lc.ny, iy), mg_pax(Lf.nz, Lc.nz, iz), e);
+    const MgPx px = mg_pax(Lf.nx, Lc.nx, ix);
+    MgPx py = AX == 1 ? mg_pax(S.ngf, S.ngc, S.of + iy) : mg_pax(Lf.ny, Lc.ny, iy);
+    MgPx pz = AX == 2 ? mg_pax(S.ngf, S.ngc, S.of + iz) : mg_pax(Lf.nz, Lc.nz, iz);
+    if (AX == 1) py.j -= S.oc;
+    if (AX == 2) pz.j -= S.oc;
+    return mg_prolong_ax<7, AX>(Lc, px, py, pz, e, AX == 1 ? -1 : 0, AX == 1 ? Lc.ny + 1 : Lc.ny, AX == 2 ? -1 : 0,
+                                AX == 2 ? Lc.nz + 1 : Lc.nz);
 }
 
-// ------------------------------------------------------------------------------ per-level kernels
+// ------------------------------------------------------------------------------ per-level kernels (AX: one rank or slabs)
 __global__ __launch_bounds__(kBlock) void k_mg_sweep0(int n, double omega, double* x, const double* b,
                                                      const double* __restrict__ idg) {
     NK_CHUNKED(i, n) x[i] = mg_sweep0_pt(omega, b, idg, (int)i);
 }
 // xn must not alias x (the ping-pong pair); b is only read at the point written
+template <int AX>
 __global__ __launch_bounds__(kBlock) void k_mg_sweep(MgLv L, double omega, double om1, double* xn, const double* __restrict__ x,
                                                     const double* b, const double* __restrict__ idg) {
-    NK_CHUNKED(i, L.n) xn[i] = mg_sweep_pt(L, omega, om1, x, b, idg, (int)i);
+    NK_CHUNKED(i, L.n) xn[i] = mg_sweep_pt<AX>(L, omega, om1, x, b, idg, (int)i);
 }
 // The sweep that writes the cycle's result z: the same per-point arithmetic times sigma (+-1: exact), and with RED the
 // partials of <b, z> (b = the cycle's input v, read at the point written anyway) in a fixed order, no atomics
@@ -179,7 +176,7 @@ __global__ __launch_bounds__(kBlock) void k_mg_sweep0_z(int n, double omega, dou
     }
     if (RED) publish(acc, part, fin, sh);
 }
-template <bool RED>
+template <int AX, bool RED>
 __global__ __launch_bounds__(kBlock) void k_mg_sweep_z(MgLv L, double omega, double om1, double sigma, double* z,
                                                       const double* __restrict__ x, const double* b, const double* __restrict__ idg,
                                                       double* __restrict__ part, int fin) {
@@ -187,21 +184,27 @@ __global__ __launch_bounds__(kBlock) void k_mg_sweep_z(MgLv L, double omega, dou
     double acc = 0.0;
     NK_CHUNKED(i, L.n) {
         const double bi = b[i];
-        const double zi = sigma * mg_sweep_pt(L, omega, om1, x, b, idg, (int)i);
+        const double zi = sigma * mg_sweep_pt<AX>(L, omega, om1, x, b, idg, (int)i);
         z[i] = zi;
         if (RED) acc = fma(bi, zi, acc);
     }
     if (RED) publish(acc, part, fin, sh);
 }
+template <int AX>
 __global__ __launch_bounds__(kBlock) void k_mg_resid(MgLv L, double* __restrict__ r, const double* __restrict__ x,
                                                     const double* __restrict__ b, const double* __restrict__ dg) {
-    NK_CHUNKED(i, L.n) r[i] = mg_resid_pt(L, x, b, dg, (int)i);
+    NK_CHUNKED(i, L.n) r[i] = mg_resid_pt<AX>(L, x, b, dg, (int)i);
 }
-__global__ __launch_bounds__(kBlock) void k_mg_restrict(MgLv Lf, MgLv Lc, double* __restrict__ bc, const double* __restrict__ r) {
-    NK_CHUNKED(j, Lc.n) bc[j] = mg_restrict_pt(Lf, Lc, r, (int)j);
+// (S is read by the slab forms only)
+template <int AX>
+__global__ __launch_bounds__(kBlock) void k_mg_restrict(MgLv Lf, MgLv Lc, MgSl S, double* __restrict__ bc,
+                                                       const double* __restrict__ r) {
+    NK_CHUNKED(j, Lc.n) bc[j] = mg_restrict_pt<AX>(Lf, Lc, r, (int)j, S);
 }
-__global__ __launch_bounds__(kBlock) void k_mg_prolong(MgLv Lf, MgLv Lc, double* __restrict__ x, const double* __restrict__ e) {
-    NK_CHUNKED(i, Lf.n) x[i] = x[i] + mg_prolong_pt(Lf, Lc, e, (int)i);
+template <int AX>
+__global__ __launch_bounds__(kBlock) void k_mg_prolong(MgLv Lf, MgLv Lc, MgSl S, double* __restrict__ x,
+                                                      const double* __restrict__ e) {
+    NK_CHUNKED(i, Lf.n) x[i] = x[i] + mg_prolong_pt<AX>(Lf, Lc, e, (int)i, S);
 }
 // The transfers between two levels of a semicoarsened plan, instantiated on the set MASK of coarsened axes (a proper
 // subset of the used axes; all of them is the kernel above).  The block is 2^lbx points of a grid row by
@@ -241,124 +244,6 @@ __global__ __launch_bounds__(kBlock) void k_mg_prolong_m(MgLv Lf, MgLv Lc, int l
         x[i] = x[i] + mg_prolong_ax<MASK>(Lc, px, py, pz, e);
     }
 }
-// ------------------------------------------------------------------------------ slab forms (a distributed hierarchy)
-// The level's rows along the slowest axis are split over the ranks (equal slabs); every level array carries one ghost
-// plane before and after its interior, which the separate-launch exchange fills with the neighbours' boundary planes
-// (zero, as allocated, on the physical side of the first and last rank).  AX = the slab axis (1: y of a 2D grid,
-// 2: z of a 3D grid).  L holds the LOCAL extents.  Along AX the kernels read the ghost plane where the one-rank
-// kernels substitute 0 -- the same value -- and the transfers take their weights from the GLOBAL row and the GLOBAL
-// extents; only the memory row is local.  Per point the same expressions, fma order and final division as above.
-struct MgSl {
-    int ngf, ngc;  // global extents of the fine / coarse level along the slab axis
-    int of, oc;    // this rank's first global row (0-based) on the fine / coarse level
-};
-template <int AX>
-__device__ __forceinline__ double mg_off_s(const MgLv& L, const double* x, int i) {
-    const int ix = i % L.nx, t = i / L.nx, iy = t % L.ny;
-    const double xm = ix > 0 ? x[i - 1] : 0.0, xp = ix + 1 < L.nx ? x[i + 1] : 0.0;
-    double o = L.cx * (xm + xp);
-    if (AX == 1) {
-        const double ym = x[i - L.nx], yp = x[i + L.nx];
-        o = o + L.cy * (ym + yp);
-    } else {
-        if (L.ny > 1) {
-            const double ym = iy > 0 ? x[i - L.nx] : 0.0, yp = iy + 1 < L.ny ? x[i + L.nx] : 0.0;
-            o = o + L.cy * (ym + yp);
-        }
-        const int pl = L.nx * L.ny;
-        const double zm = x[i - pl], zp = x[i + pl];
-        o = o + L.cz * (zm + zp);
-    }
-    return o;
-}
-template <int AX>
-__device__ __forceinline__ double mg_sweep_pt_s(const MgLv& L, double omega, double om1, const double* x, const double* b,
-                                                const double* idg, int i) {
-    const double t = b[i] - mg_off_s<AX>(L, x, i);
-    return om1 * x[i] + omega * (idg[i] * t);
-}
-template <int AX>
-__device__ __forceinline__ double mg_restrict_pt_s(const MgLv& Lf, const MgLv& Lc, const MgSl& S, const double* r, int j) {
-    const int jx = j % Lc.nx, t = j / Lc.nx, jy = t % Lc.ny, jz = t / Lc.ny;
-    const MgAx ax = mg_rax(Lf.nx, Lc.nx, jx);
-    MgAx ay = AX == 1 ? mg_rax(S.ngf, S.ngc, S.oc + jy) : mg_rax(Lf.ny, Lc.ny, jy);
-    MgAx az = AX == 2 ? mg_rax(S.ngf, S.ngc, S.oc + jz) : mg_rax(Lf.nz, Lc.nz, jz);
-    MgAx& as = AX == 1 ? ay : az;
-    as.lo -= S.of;  // the memory row: -1 and the slab's extent are the ghost planes
-    // one ghost plane suffices for equal slabs (tests/test_hip_multigrid_dist.py checks it exhaustively); a row
-    // beyond it is never read
-    if (as.lo < -1 || as.lo + as.cnt - 1 > (AX == 1 ? Lf.ny : Lf.nz)) return NAN;
-    return mg_restrict_ax(Lf, ax, ay, az, r);
-}
-// mg_prolong_ax<7> with the coarse rows ylo <= jy < yhi and zlo <= jz < zhi in memory (the slab axis: -1 .. extent,
-// its ghost planes; the others 0 .. extent - 1 as there)
-__device__ __forceinline__ double mg_prolong_ax_s(const MgLv& Lc, const MgPx& px, const MgPx& py, const MgPx& pz, int ylo, int yhi,
-                                                  int zlo, int zhi, const double* e) {
-    double vz[2] = {0.0, 0.0};
-    for (int c = 0; c < 2; ++c) {
-        const int jz = pz.j - 1 + c;
-        double vy[2] = {0.0, 0.0};
-        for (int b = 0; b < 2; ++b) {
-            const int jy = py.j - 1 + b;
-            double lo = 0.0, hi = 0.0;
-            if (jz >= zlo && jz < zhi && jy >= ylo && jy < yhi) {
-                const int row = (jz * Lc.ny + jy) * Lc.nx;
-                if (px.j - 1 >= 0) lo = e[row + px.j - 1];
-                if (px.j < Lc.nx) hi = e[row + px.j];
-            }
-            vy[b] = (1.0 - px.w) * lo + px.w * hi;
-        }
-        vz[c] = (1.0 - py.w) * vy[0] + py.w * vy[1];
-    }
-    return (1.0 - pz.w) * vz[0] + pz.w * vz[1];
-}
-template <int AX>
-__device__ __forceinline__ double mg_prolong_pt_s(const MgLv& Lf, const MgLv& Lc, const MgSl& S, const double* e, int i) {
-    const int ix = i % Lf.nx, t = i / Lf.nx, iy = t % Lf.ny, iz = t / Lf.ny;
-    const MgPx px = mg_pax(Lf.nx, Lc.nx, ix);
-    MgPx py = AX == 1 ? mg_pax(S.ngf, S.ngc, S.of + iy) : mg_pax(Lf.ny, Lc.ny, iy);
-    MgPx pz = AX == 2 ? mg_pax(S.ngf, S.ngc, S.of + iz) : mg_pax(Lf.nz, Lc.nz, iz);
-    if (AX == 1) py.j -= S.oc;
-    else pz.j -= S.oc;
-    return mg_prolong_ax_s(Lc, px, py, pz, AX == 1 ? -1 : 0, AX == 1 ? Lc.ny + 1 : Lc.ny, AX == 2 ? -1 : 0,
-                           AX == 2 ? Lc.nz + 1 : Lc.nz, e);
-}
-
-template <int AX>
-__global__ __launch_bounds__(kBlock) void k_mg_sweep_s(MgLv L, double omega, double om1, double* xn, const double* __restrict__ x,
-                                                      const double* b, const double* __restrict__ idg) {
-    NK_CHUNKED(i, L.n) xn[i] = mg_sweep_pt_s<AX>(L, omega, om1, x, b, idg, (int)i);
-}
-template <int AX, bool RED>
-__global__ __launch_bounds__(kBlock) void k_mg_sweep_z_s(MgLv L, double omega, double om1, double sigma, double* z,
-                                                        const double* __restrict__ x, const double* b,
-                                                        const double* __restrict__ idg, double* __restrict__ part, int fin) {
-    __shared__ double sh[kShN];
-    double acc = 0.0;
-    NK_CHUNKED(i, L.n) {
-        const double bi = b[i];
-        const double zi = sigma * mg_sweep_pt_s<AX>(L, omega, om1, x, b, idg, (int)i);
-        z[i] = zi;
-        if (RED) acc = fma(bi, zi, acc);
-    }
-    if (RED) publish(acc, part, fin, sh);
-}
-template <int AX>
-__global__ __launch_bounds__(kBlock) void k_mg_resid_s(MgLv L, double* __restrict__ r, const double* __restrict__ x,
-                                                      const double* __restrict__ b, const double* __restrict__ dg) {
-    NK_CHUNKED(i, L.n) r[i] = b[i] - (mg_off_s<AX>(L, x, (int)i) + dg[i] * x[i]);
-}
-template <int AX>
-__global__ __launch_bounds__(kBlock) void k_mg_restrict_s(MgLv Lf, MgLv Lc, MgSl S, double* __restrict__ bc,
-                                                         const double* __restrict__ r) {
-    NK_CHUNKED(j, Lc.n) bc[j] = mg_restrict_pt_s<AX>(Lf, Lc, S, r, (int)j);
-}
-template <int AX>
-__global__ __launch_bounds__(kBlock) void k_mg_prolong_s(MgLv Lf, MgLv Lc, MgSl S, double* __restrict__ x,
-                                                        const double* __restrict__ e) {
-    NK_CHUNKED(i, Lf.n) x[i] = x[i] + mg_prolong_pt_s<AX>(Lf, Lc, S, e, (int)i);
-}
-
 // set-up: diag = dsum + s (dsum = Σ_a -2 c_a, summed in axis order on the host) and 1 / diag
 __global__ __launch_bounds__(kBlock) void k_mg_diag(int n, double dsum, const double* __restrict__ s, double* __restrict__ dg,
                                                    double* __restrict__ idg) {
@@ -488,73 +373,6 @@ __global__ __launch_bounds__(kMgTailThreads) void k_mg_tail(MgTail T, double sig
 #undef MG_DG
 }
 
-// host: the level extents (all integer arithmetic)
-int mg_plan(const int64_t n0[3], int max_levels, int64_t (*ext)[3]) {
-    int64_t n[3] = {n0[0], n0[1], n0[2]};
-    int L = 0;
-    for (;;) {
-        for (int a = 0; a < 3; ++a) ext[L][a] = n[a];
-        ++L;
-        if (L == kMgMaxLevels || (max_levels > 0 && L >= max_levels)) break;
-        if (n[0] <= 3 && n[1] <= 3 && n[2] <= 3) break;
-        for (int a = 0; a < 3; ++a)
-            if (n[a] > 3) n[a] /= 2;
-    }
-    return L;
-}
-
-// host: the semicoarsened plan.  On every level only the axes whose coupling c_a = |k_a| / h_a² is at least tau times
-// the strongest one are halved (point Jacobi smooths the error along those; the weakly coupled axes wait until the
-// level is isotropic).  Double precision, in this order (the tests restate it): L_a = (n_a^0 + 1) h_a^0,
-// c_a = |k_a| ((n_a + 1) / L_a)² over the axes of more than 3 points.  The axis of c_max always qualifies, so every
-// level at least halves its points.
-int mg_plan_semi(const int64_t n0[3], const double h[3], const double k[3], double tau, int max_levels, int64_t (*ext)[3]) {
-    int64_t n[3] = {n0[0], n0[1], n0[2]};
-    double len[3];
-    for (int a = 0; a < 3; ++a) len[a] = (double)(n0[a] + 1) * h[a];
-    int L = 0;
-    for (;;) {
-        for (int a = 0; a < 3; ++a) ext[L][a] = n[a];
-        ++L;
-        if (L == kMgMaxLevels || (max_levels > 0 && L >= max_levels)) break;
-        if (n[0] <= 3 && n[1] <= 3 && n[2] <= 3) break;
-        double cc[3] = {0.0, 0.0, 0.0}, cmax = 0.0;
-        for (int a = 0; a < 3; ++a)
-            if (n[a] > 3) {
-                const double q = (double)(n[a] + 1) / len[a];
-                cc[a] = std::fabs(k[a]) * (q * q);
-                cmax = std::fmax(cmax, cc[a]);
-            }
-        const double bar = tau * cmax;
-        for (int a = 0; a < 3; ++a)
-            if (n[a] > 3 && cc[a] >= bar) n[a] /= 2;
-    }
-    return L;
-}
-
-// host: the plan of a slab-distributed grid in LOCAL extents (equal slabs of the slowest axis: every rank holds n0,
-// the global extent of that axis is nranks n0[ax]).  It is mg_plan of the global grid cut after L_d levels: level
-// l + 1 exists only while the local slab extent m_l is even, then m_{l+1} = m_l / 2 (the global nranks m_l >= 4 is
-// halved by mg_plan's rule as well; the other axes are whole on every rank).  *ax = the slab axis (1: y, 2: z).
-// Returns 0 with *why set where no distributed hierarchy exists.
-int mg_plan_slabs(const int64_t n0[3], int nranks, int max_levels, int64_t (*ext)[3], int* ax, const char** why) {
-    *why = nullptr;
-    *ax = n0[2] > 1 ? 2 : 1;
-    if (nranks < 2) *why = "a slab plan needs at least 2 ranks";
-    else if (n0[1] == 1 && n0[2] == 1) *why = "1D grids are not distributed (2D y-slabs and 3D z-slabs only)";
-    else if (n0[*ax] % 2 != 0) *why = "slabs of an odd number of planes cannot be coarsened";
-    else if ((int64_t)nranks * n0[*ax] >= ((int64_t)1 << 31)) *why = "at most 2^31 - 1 planes along the slab axis";
-    if (*why) return 0;
-    int64_t g[3] = {n0[0], n0[1], n0[2]};
-    g[*ax] *= nranks;
-    int Ld = 1;
-    for (int64_t ml = n0[*ax]; ml % 2 == 0; ml /= 2) ++Ld;
-    if (max_levels > 0) Ld = std::min(Ld, max_levels);
-    const int L = mg_plan(g, Ld, ext);  // (L == Ld: the global slab axis stays above 3 points while m_l is even)
-    for (int l = 0; l < L; ++l) ext[l][*ax] /= nranks;
-    return L;
-}
-
 }  // namespace
 }  // namespace nk
 
@@ -581,7 +399,6 @@ struct nk_mg {
     double *xa[kMgMaxLevels] = {}, *xb[kMgMaxLevels] = {}, *b[kMgMaxLevels] = {}, *s[kMgMaxLevels] = {},
            *dg[kMgMaxLevels] = {}, *idg[kMgMaxLevels] = {};
     double* part = nullptr;  // set-up: kMgMinmaxBlocks (min, max) pairs per level
-    size_t tail_lds = 0;
     // a distributed hierarchy (slabs of the slowest axis): lv holds the local extents
     int slab_ax = 0;              // 0: one rank; 1 / 2: the slab axis (y of a 2D grid, z of a 3D grid)
     int ng[kMgMaxLevels] = {};    // global extent of the level along the slab axis (nranks x the local one)
@@ -589,6 +406,13 @@ struct nk_mg {
 };
 
 namespace {
+
+// compile-time dispatch: f(std::integral_constant<T, V>{}) for the V of the list that v equals, so that a generic
+// lambda names the kernel instantiation of a runtime AX, RED, MASK, S32 or OUT in one launch expression
+template <typename T, T... Vs, typename F>
+void mg_pick(T v, F&& f) {
+    (void)((v == Vs && (f(std::integral_constant<T, Vs>{}), true)) || ...);
+}
 
 int mg_launch_sweep0(nk_mg* m, int l, double* x, const double* b) {
     const MgLv& L = m->lv[l];
@@ -610,20 +434,22 @@ MgSl mg_slab(const nk_mg* m, int l) {
 }
 int mg_launch_sweep(nk_mg* m, int l, double* xn, const double* x, const double* b) {
     const MgLv& L = m->lv[l];
-    if (m->slab_ax) {
-        NK_TRY(mg_exchange(m, l, x));
-        return launch(m->c, "mg_sweep", 32.0 * L.n, [&] {
-            if (m->slab_ax == 1)
-                hipLaunchKernelGGL(k_mg_sweep_s<1>, dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, m->omega,
-                                   1.0 - m->omega, xn, x, b, m->idg[l]);
-            else
-                hipLaunchKernelGGL(k_mg_sweep_s<2>, dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, m->omega,
-                                   1.0 - m->omega, xn, x, b, m->idg[l]);
-        });
-    }
+    if (m->slab_ax) NK_TRY(mg_exchange(m, l, x));
     return launch(m->c, "mg_sweep", 32.0 * L.n, [&] {
-        hipLaunchKernelGGL(k_mg_sweep, dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, m->omega, 1.0 - m->omega, xn, x, b,
-                           m->idg[l]);
+        mg_pick<int, 0, 1, 2>(m->slab_ax, [&](auto AX) {
+            hipLaunchKernelGGL(k_mg_sweep<AX.value>, dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, m->omega,
+                               1.0 - m->omega, xn, x, b, m->idg[l]);
+        });
+    });
+}
+// the residual of level l's x into r (slabs: x's ghost planes first)
+int mg_launch_resid(nk_mg* m, int l, double* r, const double* x, const double* b) {
+    const MgLv& L = m->lv[l];
+    if (m->slab_ax) NK_TRY(mg_exchange(m, l, x));
+    return launch(m->c, "mg_resid", 32.0 * L.n, [&] {
+        mg_pick<int, 0, 1, 2>(m->slab_ax, [&](auto AX) {
+            hipLaunchKernelGGL(k_mg_resid<AX.value>, dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, r, x, b, m->dg[l]);
+        });
     });
 }
 // how the cycle's last launch writes z: times sigma, with the partials of <v, z> into *red when given
@@ -644,32 +470,16 @@ int mg_launch_sweep_z(nk_mg* m, double* z, const double* x, const double* b, con
     const char* name = x ? (o.red ? "mg_sweep_dot" : "mg_sweep") : (o.red ? "mg_sweep0_dot" : "mg_sweep0");
     if (x && m->slab_ax) NK_TRY(mg_exchange(m, 0, x));
     return launch(c, name, (x ? 32.0 : 24.0) * L.n, [&] {
-        if (x && m->slab_ax) {
-            const double om = m->omega, om1 = 1.0 - m->omega;
-            if (m->slab_ax == 1 && o.red)
-                hipLaunchKernelGGL((k_mg_sweep_z_s<1, true>), dim3(g), dim3(kBlock), 0, c->stream, L, om, om1, o.sigma, z, x, b,
-                                   m->idg[0], part, fin);
-            else if (m->slab_ax == 1)
-                hipLaunchKernelGGL((k_mg_sweep_z_s<1, false>), dim3(g), dim3(kBlock), 0, c->stream, L, om, om1, o.sigma, z, x, b,
-                                   m->idg[0], part, fin);
-            else if (o.red)
-                hipLaunchKernelGGL((k_mg_sweep_z_s<2, true>), dim3(g), dim3(kBlock), 0, c->stream, L, om, om1, o.sigma, z, x, b,
+        mg_pick<bool, false, true>(o.red != nullptr, [&](auto RED) {
+            if (!x)
+                hipLaunchKernelGGL(k_mg_sweep0_z<RED.value>, dim3(g), dim3(kBlock), 0, c->stream, L.n, m->omega, o.sigma, z, b,
                                    m->idg[0], part, fin);
             else
-                hipLaunchKernelGGL((k_mg_sweep_z_s<2, false>), dim3(g), dim3(kBlock), 0, c->stream, L, om, om1, o.sigma, z, x, b,
-                                   m->idg[0], part, fin);
-        } else if (x && o.red)
-            hipLaunchKernelGGL(k_mg_sweep_z<true>, dim3(g), dim3(kBlock), 0, c->stream, L, m->omega, 1.0 - m->omega, o.sigma, z, x, b,
-                               m->idg[0], part, fin);
-        else if (x)
-            hipLaunchKernelGGL(k_mg_sweep_z<false>, dim3(g), dim3(kBlock), 0, c->stream, L, m->omega, 1.0 - m->omega, o.sigma, z, x, b,
-                               m->idg[0], part, fin);
-        else if (o.red)
-            hipLaunchKernelGGL(k_mg_sweep0_z<true>, dim3(g), dim3(kBlock), 0, c->stream, L.n, m->omega, o.sigma, z, b, m->idg[0], part,
-                               fin);
-        else
-            hipLaunchKernelGGL(k_mg_sweep0_z<false>, dim3(g), dim3(kBlock), 0, c->stream, L.n, m->omega, o.sigma, z, b, m->idg[0], part,
-                               fin);
+                mg_pick<int, 0, 1, 2>(m->slab_ax, [&](auto AX) {
+                    hipLaunchKernelGGL((k_mg_sweep_z<AX.value, RED.value>), dim3(g), dim3(kBlock), 0, c->stream, L, m->omega,
+                                       1.0 - m->omega, o.sigma, z, x, b, m->idg[0], part, fin);
+                });
+        });
     });
 }
 // `sweeps` sweeps on level l after `done` earlier ones; the x so far is *cur (unused when done == 0), the sweeps
@@ -687,34 +497,17 @@ int mg_sweeps(nk_mg* m, int l, const double* b, int done, int sweeps, double** c
     return NK_OK;
 }
 
-// Which transfer kernels a level pair runs.  mask = the coarsened axes when they are a proper subset of the used ones
-// (a semicoarsened level: the k_mg_*_m instantiation of that mask), 0 = the general kernels (every used axis
-// coarsened, today's levels).  The names of the profiler classes carry the mask: mg_restrict_x, mg_prolong_yz, ...
-struct MgXfer {
-    int mask;
-    bool s32;
-    bool general;  // the kernel-variant bench build forces the general kernels under the mask's class name
-};
+// Which transfer kernels the level pair l, l + 1 runs: nk_mg_plan.hpp's rule on the one-rank extents (slabs: the
+// slab forms of the general kernels).  The names of the profiler classes carry the mask: mg_restrict_x, mg_prolong_yz, ...
 MgXfer mg_xfer(const nk_mg* m, int l) {
-    // the kernel-variant bench build can force the general kernels, to time both on the same level pair
+    // the kernel-variant bench build can force the general kernels under the mask's class name, to time both on the
+    // same level pair
     static const bool generic = NK_TUNE("NK_MG_GENERIC", 0) != 0;
     const MgLv &Lf = m->lv[l], &Lc = m->lv[l + 1];
     const int nf[3] = {Lf.nx, Lf.ny, Lf.nz}, nc[3] = {Lc.nx, Lc.ny, Lc.nz};
-    int mask = 0, used = 0;
-    bool s32 = true;
-    for (int a = 0; a < 3; ++a) {
-        if (nf[a] > 1) used |= 1 << a;
-        if (nf[a] != nc[a]) {
-            mask |= 1 << a;
-            s32 = s32 && (int64_t)(nf[a] + 4) * (nc[a] + 2) < ((int64_t)1 << 31);
-        }
-    }
-    // axes of at most 3 points that stay as they are while every other one is coarsened: also today's levels
-    bool rest_small = true;
-    for (int a = 0; a < 3; ++a)
-        if (nf[a] == nc[a] && nf[a] > 3) rest_small = false;
-    if (mask == 0 || mask == used || rest_small) return MgXfer{0, false, true};
-    return MgXfer{mask, s32, generic};
+    MgXfer t = m->slab_ax ? MgXfer{0, false, true} : nk::mg_xfer(nf, nc);
+    t.general = t.general || generic;
+    return t;
 }
 const char* const kMgRestrictName[7] = {"mg_restrict",    "mg_restrict_x",  "mg_restrict_y", "mg_restrict_xy",
                                         "mg_restrict_z",  "mg_restrict_xz", "mg_restrict_yz"};
@@ -722,83 +515,47 @@ const char* const kMgSetupName[7] = {"mg_setup_restrict",    "mg_setup_restrict_
                                      "mg_setup_restrict_z",  "mg_setup_restrict_xz", "mg_setup_restrict_yz"};
 const char* const kMgProlongName[7] = {"mg_prolong",   "mg_prolong_x",  "mg_prolong_y", "mg_prolong_xy",
                                        "mg_prolong_z", "mg_prolong_xz", "mg_prolong_yz"};
-// grid of the row-shaped kernels for rows of nx points: 2^lbx = the block's extent along x (4 .. 64, the smallest
-// that covers a short row), about eight rows per thread, at most kRedCap - 2 blocks as the streaming kernels
-struct MgRows {
-    dim3 grid;
-    int lbx;
-};
-MgRows mg_rows(int nx, int64_t rows) {
-    int lbx = 6;
-    while (lbx > 2 && (1 << (lbx - 1)) >= nx) --lbx;
-    const int64_t gx = ((int64_t)nx + (1 << lbx) - 1) >> lbx, rpb = kBlock >> lbx;
-    int64_t gy = (rows + 8 * rpb - 1) / (8 * rpb);
-    gy = std::min<int64_t>(gy, std::max<int64_t>(1, (kRedCap - 2) / gx));
-    gy = std::min<int64_t>(gy, 65535);
-    return MgRows{dim3((unsigned)gx, (unsigned)gy), lbx};
-}
-template <int MASK>
-void mg_restrict_m(nk_mg* m, const MgLv& Lf, const MgLv& Lc, bool s32, double* bc, const double* r) {
-    const MgRows g = mg_rows(Lc.nx, (int64_t)Lc.ny * Lc.nz);
-    if (s32) hipLaunchKernelGGL((k_mg_restrict_m<MASK, true>), g.grid, dim3(kBlock), 0, m->c->stream, Lf, Lc, g.lbx, bc, r);
-    else hipLaunchKernelGGL((k_mg_restrict_m<MASK, false>), g.grid, dim3(kBlock), 0, m->c->stream, Lf, Lc, g.lbx, bc, r);
-}
-template <int MASK>
-void mg_prolong_m(nk_mg* m, const MgLv& Lf, const MgLv& Lc, bool s32, double* x, const double* e) {
-    const MgRows g = mg_rows(Lf.nx, (int64_t)Lf.ny * Lf.nz);
-    if (s32) hipLaunchKernelGGL((k_mg_prolong_m<MASK, true>), g.grid, dim3(kBlock), 0, m->c->stream, Lf, Lc, g.lbx, x, e);
-    else hipLaunchKernelGGL((k_mg_prolong_m<MASK, false>), g.grid, dim3(kBlock), 0, m->c->stream, Lf, Lc, g.lbx, x, e);
-}
 
-// setup: the restriction of s during set-up (a profiler class of its own)
+// The transfers: the general kernel in its AX form (slabs: the source's ghost planes first), or the instantiation on
+// the mask of a semicoarsened level pair.  setup: the restriction of s during set-up (a profiler class of its own)
 int mg_restrict(nk_mg* m, int l, double* bc, const double* r, bool setup) {
     const MgLv &Lf = m->lv[l], &Lc = m->lv[l + 1];
-    if (m->slab_ax) {  // slabs: r's ghost planes first, then the slab form of the general kernel
-        NK_TRY(mg_exchange(m, l, r));
-        const MgSl S = mg_slab(m, l);
-        return launch(m->c, (setup ? kMgSetupName : kMgRestrictName)[0], 8.0 * Lf.n + 8.0 * Lc.n, [&] {
-            if (m->slab_ax == 1)
-                hipLaunchKernelGGL(k_mg_restrict_s<1>, dim3(wide_blocks(Lc.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, S, bc, r);
-            else
-                hipLaunchKernelGGL(k_mg_restrict_s<2>, dim3(wide_blocks(Lc.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, S, bc, r);
-        });
-    }
+    if (m->slab_ax) NK_TRY(mg_exchange(m, l, r));
     const MgXfer t = mg_xfer(m, l);
+    const MgSl S = mg_slab(m, l);
+    const MgRows g = mg_rows(Lc.nx, (int64_t)Lc.ny * Lc.nz);
     return launch(m->c, (setup ? kMgSetupName : kMgRestrictName)[t.mask], 8.0 * Lf.n + 8.0 * Lc.n, [&] {
-        switch (t.general ? 0 : t.mask) {
-            case 1: mg_restrict_m<1>(m, Lf, Lc, t.s32, bc, r); break;
-            case 2: mg_restrict_m<2>(m, Lf, Lc, t.s32, bc, r); break;
-            case 3: mg_restrict_m<3>(m, Lf, Lc, t.s32, bc, r); break;
-            case 4: mg_restrict_m<4>(m, Lf, Lc, t.s32, bc, r); break;
-            case 5: mg_restrict_m<5>(m, Lf, Lc, t.s32, bc, r); break;
-            case 6: mg_restrict_m<6>(m, Lf, Lc, t.s32, bc, r); break;
-            default: hipLaunchKernelGGL(k_mg_restrict, dim3(wide_blocks(Lc.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, bc, r);
-        }
+        if (t.general)
+            mg_pick<int, 0, 1, 2>(m->slab_ax, [&](auto AX) {
+                hipLaunchKernelGGL(k_mg_restrict<AX.value>, dim3(wide_blocks(Lc.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, S, bc, r);
+            });
+        else
+            mg_pick<int, 1, 2, 3, 4, 5, 6>(t.mask, [&](auto MASK) {
+                mg_pick<bool, false, true>(t.s32, [&](auto S32) {
+                    hipLaunchKernelGGL((k_mg_restrict_m<MASK.value, S32.value>), dim3(g.gx, g.gy), dim3(kBlock), 0, m->c->stream, Lf,
+                                       Lc, g.lbx, bc, r);
+                });
+            });
     });
 }
 int mg_prolong(nk_mg* m, int l, double* x, const double* e) {
     const MgLv &Lf = m->lv[l], &Lc = m->lv[l + 1];
-    if (m->slab_ax) {  // slabs: the coarse e's ghost planes first
-        NK_TRY(mg_exchange(m, l + 1, e));
-        const MgSl S = mg_slab(m, l);
-        return launch(m->c, kMgProlongName[0], 16.0 * Lf.n + 8.0 * Lc.n, [&] {
-            if (m->slab_ax == 1)
-                hipLaunchKernelGGL(k_mg_prolong_s<1>, dim3(wide_blocks(Lf.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, S, x, e);
-            else
-                hipLaunchKernelGGL(k_mg_prolong_s<2>, dim3(wide_blocks(Lf.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, S, x, e);
-        });
-    }
+    if (m->slab_ax) NK_TRY(mg_exchange(m, l + 1, e));
     const MgXfer t = mg_xfer(m, l);
+    const MgSl S = mg_slab(m, l);
+    const MgRows g = mg_rows(Lf.nx, (int64_t)Lf.ny * Lf.nz);
     return launch(m->c, kMgProlongName[t.mask], 16.0 * Lf.n + 8.0 * Lc.n, [&] {
-        switch (t.general ? 0 : t.mask) {
-            case 1: mg_prolong_m<1>(m, Lf, Lc, t.s32, x, e); break;
-            case 2: mg_prolong_m<2>(m, Lf, Lc, t.s32, x, e); break;
-            case 3: mg_prolong_m<3>(m, Lf, Lc, t.s32, x, e); break;
-            case 4: mg_prolong_m<4>(m, Lf, Lc, t.s32, x, e); break;
-            case 5: mg_prolong_m<5>(m, Lf, Lc, t.s32, x, e); break;
-            case 6: mg_prolong_m<6>(m, Lf, Lc, t.s32, x, e); break;
-            default: hipLaunchKernelGGL(k_mg_prolong, dim3(wide_blocks(Lf.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, x, e);
-        }
+        if (t.general)
+            mg_pick<int, 0, 1, 2>(m->slab_ax, [&](auto AX) {
+                hipLaunchKernelGGL(k_mg_prolong<AX.value>, dim3(wide_blocks(Lf.n)), dim3(kBlock), 0, m->c->stream, Lf, Lc, S, x, e);
+            });
+        else
+            mg_pick<int, 1, 2, 3, 4, 5, 6>(t.mask, [&](auto MASK) {
+                mg_pick<bool, false, true>(t.s32, [&](auto S32) {
+                    hipLaunchKernelGGL((k_mg_prolong_m<MASK.value, S32.value>), dim3(g.gx, g.gy), dim3(kBlock), 0, m->c->stream, Lf,
+                                       Lc, g.lbx, x, e);
+                });
+            });
     });
 }
 
@@ -907,39 +664,40 @@ int mg_setup(nk_mg* m, const double k[3], const nk_problem* jac, const double* u
     return NK_OK;
 }
 
+// the plan ABI's shared argument check and copy-out (the first `cap` levels; *nlevels is the plan's count)
+bool mg_plan_args(const int64_t* n, int32_t max_levels, const int64_t* extents, int32_t cap, const int32_t* nlevels) {
+    return n && nlevels && n[0] >= 1 && n[1] >= 1 && n[2] >= 1 && max_levels >= 0 && cap >= 0 && (cap == 0 || extents);
+}
+int mg_plan_out(const int64_t (*ext)[3], int L, int64_t* extents, int32_t cap, int32_t* nlevels) {
+    for (int l = 0; l < L && l < cap; ++l)
+        for (int a = 0; a < 3; ++a) extents[3 * l + a] = ext[l][a];
+    *nlevels = L;
+    return NK_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int nk_mg_plan(const int64_t n[3], int32_t max_levels, int64_t* extents, int32_t cap, int32_t* nlevels) {
-    if (!n || !nlevels || n[0] < 1 || n[1] < 1 || n[2] < 1 || max_levels < 0 || cap < 0 || (cap > 0 && !extents)) return NK_E_ARG;
+    if (!mg_plan_args(n, max_levels, extents, cap, nlevels)) return NK_E_ARG;
     int64_t ext[kMgMaxLevels][3];
-    const int L = mg_plan(n, max_levels, ext);
-    for (int l = 0; l < L && l < cap; ++l)
-        for (int a = 0; a < 3; ++a) extents[3 * l + a] = ext[l][a];
-    *nlevels = L;
-    return NK_OK;
+    return mg_plan_out(ext, mg_plan(n, max_levels, ext), extents, cap, nlevels);
 }
 
 int nk_mg_plan_slabs(const int64_t n_local[3], int32_t nranks, int32_t max_levels, int64_t* extents, int32_t cap,
                      int32_t* nlevels) {
-    if (!n_local || !nlevels || n_local[0] < 1 || n_local[1] < 1 || n_local[2] < 1 || max_levels < 0 || cap < 0 ||
-        (cap > 0 && !extents))
-        return NK_E_ARG;
+    if (!mg_plan_args(n_local, max_levels, extents, cap, nlevels)) return NK_E_ARG;
     int64_t ext[kMgMaxLevels][3];
     int ax = 0;
     const char* why = nullptr;
     const int L = mg_plan_slabs(n_local, nranks, max_levels, ext, &ax, &why);
-    if (L == 0) return NK_E_ARG;
-    for (int l = 0; l < L && l < cap; ++l)
-        for (int a = 0; a < 3; ++a) extents[3 * l + a] = ext[l][a];
-    *nlevels = L;
-    return NK_OK;
+    return L == 0 ? NK_E_ARG : mg_plan_out(ext, L, extents, cap, nlevels);
 }
 
 int nk_mg_plan_semi(const int64_t n[3], const double h[3], const double k[3], double threshold, int32_t max_levels,
                     int64_t* extents, int32_t cap, int32_t* nlevels) {
-    if (!n || !h || !nlevels || n[0] < 1 || n[1] < 1 || n[2] < 1 || max_levels < 0 || cap < 0 || (cap > 0 && !extents)) return NK_E_ARG;
+    if (!h || !mg_plan_args(n, max_levels, extents, cap, nlevels)) return NK_E_ARG;
     if (!(threshold == 0.0 || (threshold > 0.0 && threshold <= 1.0))) return NK_E_ARG;
     double kk[3] = {1.0, 1.0, 1.0};
     for (int a = 0; a < 3; ++a) {
@@ -949,11 +707,7 @@ int nk_mg_plan_semi(const int64_t n[3], const double h[3], const double k[3], do
     }
     const double hh[3] = {n[0] == 1 ? 1.0 : h[0], n[1] == 1 ? 1.0 : h[1], n[2] == 1 ? 1.0 : h[2]};
     int64_t ext[kMgMaxLevels][3];
-    const int L = mg_plan_semi(n, hh, kk, threshold == 0.0 ? 0.5 : threshold, max_levels, ext);
-    for (int l = 0; l < L && l < cap; ++l)
-        for (int a = 0; a < 3; ++a) extents[3 * l + a] = ext[l][a];
-    *nlevels = L;
-    return NK_OK;
+    return mg_plan_out(ext, mg_plan_semi(n, hh, kk, threshold == 0.0 ? 0.5 : threshold, max_levels, ext), extents, cap, nlevels);
 }
 
 }  // extern "C"
@@ -990,25 +744,9 @@ int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int6
     int64_t ext[kMgMaxLevels][3];
     int nlev = 0, slab_ax = 0;
     if (given) {
-        if (nlevels < 1 || nlevels > kMgMaxLevels) return fail(c, NK_E_ARG, "multigrid: the level list has fewer than 1 or more than 32 levels");
-        for (int a = 0; a < 3; ++a)
-            if (given[a] != n0[a]) return fail(c, NK_E_ARG, "multigrid: level 0 of the level list is not the problem's grid");
-        for (int l = 0; l < nlevels; ++l) {
-            bool coarsened = false;
-            for (int a = 0; a < 3; ++a) {
-                const int64_t v = given[3 * l + a];
-                ext[l][a] = v;
-                if (l == 0) continue;
-                const int64_t f = given[3 * (l - 1) + a];
-                if (v == f) continue;
-                if (!(f > 3 && v == f / 2))
-                    return fail(c, NK_E_ARG, "multigrid: level " + std::to_string(l) + " of the level list: an axis is neither kept nor "
-                                             "n / 2 of an axis of more than 3 points");
-                coarsened = true;
-            }
-            if (l > 0 && !coarsened)
-                return fail(c, NK_E_ARG, "multigrid: level " + std::to_string(l) + " of the level list coarsens no axis");
-        }
+        char buf[128];
+        if (const char* why = mg_levels_why(n0, given, nlevels, buf)) return fail(c, NK_E_ARG, std::string("multigrid: ") + why);
+        std::copy(given, given + 3 * nlevels, &ext[0][0]);
         nlev = nlevels;
     } else if (dist) {
         const char* why = nullptr;
@@ -1031,19 +769,19 @@ int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int6
         // slabs: the length of the global grid along the slab axis, as the one-rank hierarchy of that grid has it
         m->len[a] = (double)((a == slab_ax && dist ? c->nranks * n0[a] : n0[a]) + 1) * h[a];
     }
-    m->tail = m->nlev_alloc;
+    // (a distributed hierarchy has no tail: every level runs the per-level kernels, with exchanges between them)
+    const MgTailPlan tail = dist ? MgTailPlan{nlev, 0} : mg_tail_plan(ext, nlev);
+    m->tail = tail.first;
     for (int l = 0; l < m->nlev_alloc; ++l) {
         MgLv& L = m->lv[l];
         L.nx = (int)ext[l][0]; L.ny = (int)ext[l][1]; L.nz = (int)ext[l][2];
         L.n = L.nx * L.ny * L.nz;
         L.cx = L.cy = L.cz = 0.0;
-        // (a distributed hierarchy has no tail: every level runs the per-level kernels, with exchanges between them)
-        if (!dist && m->tail == m->nlev_alloc && L.n <= kMgTailPoints && m->nlev_alloc - l <= kMgTailLevels) m->tail = l;
         const size_t bytes = sizeof(double) * (size_t)L.n;
         bool ok = true;
         // slabs: xa, xb, s, b carry one ghost plane before and after the interior, zero from here on where no
         // neighbour writes it (the physical side of the first and last rank: the Dirichlet boundary)
-        const int64_t gh = dist ? (int64_t)L.nx * (slab_ax == 2 ? L.ny : 1) : 0;
+        const int64_t gh = mg_ghost(ext[l], slab_ax);
         if (dist) m->ng[l] = (int)(c->nranks * ext[l][slab_ax]);
         m->ghost[l] = gh;
         auto with_ghosts = [&](double** q) {
@@ -1071,11 +809,8 @@ int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int6
         return fail(c, NK_E_NOMEM, "multigrid: out of device memory");
     }
     if (m->tail < m->nlev_alloc) {
-        size_t pts = 0;
-        for (int l = m->tail; l < m->nlev_alloc; ++l) pts += (size_t)m->lv[l].n;
-        m->tail_lds = 5 * sizeof(double) * pts;
         // the same limit for every hierarchy (a per-hierarchy value could lower it under an earlier, larger tail)
-        hipError_t e = m->tail_lds <= kMgTailLds ? hipSuccess : hipErrorInvalidValue;
+        hipError_t e = tail.lds <= kMgTailLds ? hipSuccess : hipErrorInvalidValue;
         for (const void* f : {reinterpret_cast<const void*>(k_mg_tail<0>), reinterpret_cast<const void*>(k_mg_tail<1>),
                               reinterpret_cast<const void*>(k_mg_tail<2>)})
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMgTailLds);
@@ -1197,16 +932,7 @@ int nk::mg_apply_red(nk_mg* m, double* z, const double* v, Red* red) {
         }
         NK_TRY(mg_sweeps(m, l, b, 0, m->nu, &cur[l], nullptr, out));
         double* r = cur[l] == m->xa[l] ? m->xb[l] : m->xa[l];
-        const MgLv& Lv = m->lv[l];
-        if (m->slab_ax) NK_TRY(mg_exchange(m, l, cur[l]));
-        NK_TRY(launch(c, "mg_resid", 32.0 * Lv.n, [&] {
-            if (m->slab_ax == 1)
-                hipLaunchKernelGGL(k_mg_resid_s<1>, dim3(wide_blocks(Lv.n)), dim3(kBlock), 0, c->stream, Lv, r, cur[l], b, m->dg[l]);
-            else if (m->slab_ax == 2)
-                hipLaunchKernelGGL(k_mg_resid_s<2>, dim3(wide_blocks(Lv.n)), dim3(kBlock), 0, c->stream, Lv, r, cur[l], b, m->dg[l]);
-            else
-                hipLaunchKernelGGL(k_mg_resid, dim3(wide_blocks(Lv.n)), dim3(kBlock), 0, c->stream, Lv, r, cur[l], b, m->dg[l]);
-        }));
+        NK_TRY(mg_launch_resid(m, l, r, cur[l], b));
         NK_TRY(mg_restrict(m, l, m->b[l + 1], r, false));
     }
     if (G < L) {
@@ -1234,9 +960,10 @@ int nk::mg_apply_red(nk_mg* m, double* z, const double* v, Red* red) {
         int fin = 0;
         double* part = mode == 2 ? red_out(c, 1, red, &fin) : nullptr;
         NK_TRY(launch(c, mode == 2 ? "mg_tail_dot" : "mg_tail", 16.0 * pts + 16.0 * m->lv[G].n, [&] {
-            if (mode == 2) hipLaunchKernelGGL(k_mg_tail<2>, dim3(1), dim3(kMgTailThreads), lds, c->stream, T, out.sigma, part, fin);
-            else if (mode == 1) hipLaunchKernelGGL(k_mg_tail<1>, dim3(1), dim3(kMgTailThreads), lds, c->stream, T, out.sigma, part, fin);
-            else hipLaunchKernelGGL(k_mg_tail<0>, dim3(1), dim3(kMgTailThreads), lds, c->stream, T, 1.0, part, fin);
+            mg_pick<int, 0, 1, 2>(mode, [&](auto OUT) {
+                hipLaunchKernelGGL(k_mg_tail<OUT.value>, dim3(1), dim3(kMgTailThreads), lds, c->stream, T, mode ? out.sigma : 1.0,
+                                   part, fin);
+            });
         }));
     }
     // ascent
