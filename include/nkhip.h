@@ -52,6 +52,12 @@ extern "C" {
 #define NK_USER2D 17       /* on a 1D / 2D / 3D grid (the kind fixes the slab axis, as for the      */
 #define NK_USER3D 18       /* built-in kinds)                                                      */
 
+/* the implicit schemes composed with f(u) = a Δu + λ exp(u), the solid-fuel-ignition problem u_t = a Δu + λ exp(u)
+ * (DESIGN.md §13): 2D, one rank, bc_zero!; λ, a, Δt, u_n (and α) of nk_problem.  Numbered beyond NK_USER3D */
+#define NK_IGNITION2D_EULER 20      /* (u_n + Δt f(u)) - u                                  */
+#define NK_IGNITION2D_MIDPOINT 21   /* (u_n + Δt f(α u_n + (1 - α) u)) - u                  */
+#define NK_IGNITION2D_TRAPEZOID 22  /* (u_n + (Δt / 2) (f(u_n) + f(u))) - u                 */
+
 #define NK_BC_ZERO 0       /* bc_zero!, examples/heat_2D.jl:28-38 */
 #define NK_BC_PERIODIC 1   /* bc_periodic!, examples/heat_2D.jl:15-26 (heat kinds; every extent >= 3):
                               x / y wrap inside the kernels, the slab axis through the ghost planes
@@ -114,17 +120,17 @@ typedef struct nk_user_ops {
  * spacings are global (h = 1/(N_global + 1)).  x is the fastest axis (the reference's
  * column-major first index). */
 typedef struct nk_problem {
-    int32_t kind;           /* NK_BRATU1D … NK_BRATU3D, NK_USER1D … NK_USER3D */
+    int32_t kind;           /* NK_BRATU1D … NK_BRATU3D, NK_USER1D … NK_USER3D, NK_IGNITION2D_* */
     int32_t bc;             /* NK_BC_ZERO / NK_BC_PERIODIC */
     int64_t nx, ny, nz;     /* local interior extents (ny = nz = 1 in 1D, nz = 1 in 2D) */
     double hx, hy, hz;      /* grid spacings */
-    double lambda;          /* Bratu λ */
-    double a, dt;           /* heat diffusivity and time step Δt */
-    const double* un;       /* heat: device interior pointer to u_n (borrowed for the call).  Midpoint /
+    double lambda;          /* Bratu / ignition λ */
+    double a, dt;           /* heat / ignition diffusivity and time step Δt */
+    const double* un;       /* heat / ignition: device interior pointer to u_n (borrowed for the call).  Midpoint /
                                trapezoid read its neighbours too: it must be an nk_vec_alloc grid function
                                (its ghost planes are exchanged / wrapped by the library) */
     const nk_user_ops* user;  /* NK_USER*: the callbacks (borrowed for the call) */
-    double alpha;           /* NK_HEAT*_MIDPOINT: G_Midpoint!'s α (the reference's default is 0.5) */
+    double alpha;           /* NK_HEAT*_MIDPOINT, NK_IGNITION2D_MIDPOINT: G_Midpoint!'s α (the reference's default is 0.5) */
 } nk_problem;
 
 /* ---------------------------------------------------------------- context / memory */

@@ -8,13 +8,14 @@ from .ariadne import (EisenstatWalker, Fixed, Forcing, JacobianOperator, Result,
                       newton_krylov_)
 from .device import Context, DeviceArray, Grid, default_context, set_default_context
 from .distributed import block, dist_unique_id, init_distributed, slab
-from .implicit import G_Euler_, G_Midpoint_, G_Trapezoid_, diffusion3d_, diffusion_, solve
+from .implicit import G_Euler_, G_Midpoint_, G_Trapezoid_, diffusion3d_, diffusion_, ignition_, solve
 from .krylov import (KrylovConstructor, exp_, kaxpby_, kaxpy_, kaxpy_norm_, kcopy_, kdivcopy_, kdot, kfill_, knorm, kref_, krylov_solve_,
                      krylov_workspace, kscal_, mgs_step_)
 from .precond import (DiagonalPreconditioner, GmresPreconditioner, Ilu0Preconditioner, MultigridPreconditioner, Preconditioner,
                       UserPreconditioner, gmres_preconditioner, ilu0, jacobi, jacobian_diag, multigrid, multigrid_plan)
 from .problems import (DeviceResidual, UserResidual, bc_periodic_, bc_zero_, bratu2d_, bratu3d_, bratu_, heat2d_euler_, heat2d_midpoint_,
-                       heat2d_trapezoid_, heat3d_euler_, heat3d_midpoint_, heat3d_trapezoid_)
+                       heat2d_trapezoid_, heat3d_euler_, heat3d_midpoint_, heat3d_trapezoid_, ignition2d_euler_, ignition2d_midpoint_,
+                       ignition2d_trapezoid_)
 
 __all__ = [
     "NKError", "device_count", "load", "EisenstatWalker", "Fixed", "Forcing", "JacobianOperator", "Result", "Stats",
@@ -26,5 +27,5 @@ __all__ = [
     "jacobi", "jacobian_diag",
     "krylov_solve_", "krylov_workspace", "kscal_", "mgs_step_", "DeviceResidual", "UserResidual", "bc_zero_", "bratu2d_", "bratu3d_", "bratu_",
     "heat2d_euler_", "heat3d_euler_", "heat2d_midpoint_", "heat3d_midpoint_", "heat2d_trapezoid_", "heat3d_trapezoid_",
-    "bc_periodic_",
+    "bc_periodic_", "ignition_", "ignition2d_euler_", "ignition2d_midpoint_", "ignition2d_trapezoid_",
 ]

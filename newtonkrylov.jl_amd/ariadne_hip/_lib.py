@@ -27,6 +27,7 @@ NK_BRATU1D, NK_BRATU2D, NK_HEAT2D_EULER, NK_HEAT3D_EULER = 1, 2, 3, 4
 NK_HEAT2D_MIDPOINT, NK_HEAT3D_MIDPOINT, NK_HEAT2D_TRAPEZOID, NK_HEAT3D_TRAPEZOID = 5, 6, 7, 8
 NK_BRATU3D = 9
 NK_USER1D, NK_USER2D, NK_USER3D = 16, 17, 18
+NK_IGNITION2D_EULER, NK_IGNITION2D_MIDPOINT, NK_IGNITION2D_TRAPEZOID = 20, 21, 22
 NK_BC_ZERO, NK_BC_PERIODIC = 0, 1
 NK_JV_EXACT, NK_JV_FD = 0, 1
 NK_ALGO_GMRES, NK_ALGO_CG, NK_ALGO_FGMRES, NK_ALGO_MINRES = 0, 1, 2, 3

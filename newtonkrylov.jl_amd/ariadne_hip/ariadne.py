@@ -190,7 +190,7 @@ def collect(J, *, coloring: str | None = None):
     if coloring not in (None, "stencil"):
         raise ValueError("coloring must be 'stencil' (default) or 'dense'")
     prob = Jo.problem()
-    user = getattr(Jo.f, "kind", 0) >= _lib.NK_USER1D
+    user = _lib.NK_USER1D <= getattr(Jo.f, "kind", 0) <= _lib.NK_USER3D  # (the ignition kinds are numbered beyond)
     # (2 dim + 1) n bounds a stencil's entries; a user residual's coupling is unknown: retry with nnz
     cap = (2 * grid.dim + 1) * n if not user else min(n * n, 64 * n)
     colptr = np.zeros(n + 1, dtype=np.int64)

@@ -11,6 +11,7 @@ loop, and `JacobianOperator` maps it to the matching fused Jv kernel (nk_jv) ins
 | `bratu3d_`    | 3D generalisation of `bratu2d_`       | `(dx, dy, dz, lam)`                  |
 | `heat2d_euler_` | `G_Euler!` ∘ `diffusion!` implicit.jl:8-13 + heat_2D.jl:45-62 | `(u_n, dt, du, (a, dx, dy, bc_zero_), t)` |
 | `heat3d_euler_` | 3D generalisation                | `(u_n, dt, du, (a, dx, dy, dz, bc_zero_), t)` |
+| `ignition2d_euler_`, `ignition2d_midpoint_`, `ignition2d_trapezoid_` | the same schemes ∘ f(u) = a Δu + λ exp(u) | `(u_n, dt, du, (a, dx, dy, lam, bc_zero_), t)` |
 | `heat{2,3}d_midpoint_`, `heat{2,3}d_trapezoid_` | `G_Midpoint!` / `G_Trapezoid!` ∘ `diffusion!` implicit.jl:17-37 | as above; `bc_periodic_` (heat_2D.jl:15-26) for any heat residual |
 | `UserResidual(F[, J])` | any `F!(res, u, p)` evaluated on the device by the caller | the caller's |
 """
@@ -147,6 +148,42 @@ class _Heat(DeviceResidual):
 
 _HeatEuler = _Heat  # backwards-compatible name
 
+_IGNITION = {"G_Euler!": _lib.NK_IGNITION2D_EULER, "G_Midpoint!": _lib.NK_IGNITION2D_MIDPOINT,
+             "G_Trapezoid!": _lib.NK_IGNITION2D_TRAPEZOID}
+
+
+class _Ignition(DeviceResidual):
+    """F!(res, u, (uₙ, Δt, du, p, t)) = G!(res, uₙ, Δt, f!, du, u, p, t) for f(u) = a Δu + λ exp(u) -- the solid-fuel-
+    ignition problem u_t = a Δu + λ exp(u): diffusion!'s a * (…) plus Bratu's λ * exp(u) -- and G ∈ {G_Euler!,
+    G_Midpoint!(α), G_Trapezoid!} (implicit.jl:8-37), p = (a, Δx, Δy, λ, bc_zero_).  2D, one rank, zero Dirichlet
+    ghosts.  One fused stencil kernel per call."""
+
+    def __init__(self, scheme: str = "G_Euler!", alpha: float = 0.5):
+        self.scheme, self.alpha = scheme, float(alpha)
+        self.kind = _IGNITION[scheme]
+        a = f"(α = {self.alpha})" if scheme == "G_Midpoint!" and self.alpha != 0.5 else ""
+        self.name = f"{scheme}{a}∘ignition2d!"
+
+    def with_alpha(self, alpha: float) -> "_Ignition":
+        """G_Midpoint!(…; α) -- the keyword of implicit.jl:17."""
+        if self.scheme != "G_Midpoint!":
+            raise ValueError("α is a G_Midpoint! keyword")
+        return _Ignition(self.scheme, alpha)
+
+    def problem(self, u, p):
+        un, dt, _du, fp, _t = p
+        if u.grid.dim != 2:
+            raise ValueError(f"{self.name} needs a 2D grid")
+        a, dx, dy, lam, bc = fp
+        if bc is not bc_zero_:
+            raise NotImplementedError(f"boundary {bc!r}: the ignition kernels implement bc_zero_ only")
+        if not isinstance(un, DeviceArray) or un.grid != u.grid:
+            raise ValueError("u_n must be a DeviceArray on u's grid")
+        nx, ny, nz = u.grid.nxyz
+        return _lib.nk_problem(self.kind, _lib.NK_BC_ZERO, nx, ny, nz, float(dx), float(dy), 1.0, float(lam), float(a),
+                               float(dt), un.ptr, None, self.alpha)
+
+
 bratu_ = _Bratu1D()
 bratu2d_ = _Bratu2D()
 bratu3d_ = _Bratu3D()
@@ -156,6 +193,9 @@ heat2d_midpoint_ = _Heat(2, "G_Midpoint!")
 heat3d_midpoint_ = _Heat(3, "G_Midpoint!")
 heat2d_trapezoid_ = _Heat(2, "G_Trapezoid!")
 heat3d_trapezoid_ = _Heat(3, "G_Trapezoid!")
+ignition2d_euler_ = _Ignition()
+ignition2d_midpoint_ = _Ignition("G_Midpoint!")
+ignition2d_trapezoid_ = _Ignition("G_Trapezoid!")
 
 
 # ----------------------------------------------------------------------------- user residuals

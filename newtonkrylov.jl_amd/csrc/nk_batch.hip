@@ -47,11 +47,12 @@ constexpr int kind_dim() {
 }
 template <int KIND>
 constexpr int kind_scheme() {
-    return (KIND == NK_HEAT2D_MIDPOINT || KIND == NK_HEAT3D_MIDPOINT)
+    return (KIND == NK_HEAT2D_MIDPOINT || KIND == NK_HEAT3D_MIDPOINT || KIND == NK_IGNITION2D_MIDPOINT)
                ? 1
-               : ((KIND == NK_HEAT2D_TRAPEZOID || KIND == NK_HEAT3D_TRAPEZOID) ? 2 : 0);
+               : ((KIND == NK_HEAT2D_TRAPEZOID || KIND == NK_HEAT3D_TRAPEZOID || KIND == NK_IGNITION2D_TRAPEZOID) ? 2 : 0);
 }
 constexpr bool kind_bratu(int k) { return k == NK_BRATU1D || k == NK_BRATU2D || k == NK_BRATU3D; }
+constexpr bool kind_ignition(int k) { return k >= NK_IGNITION2D_EULER && k <= NK_IGNITION2D_TRAPEZOID; }
 
 // ((p - 2c) + m) / h^2 exactly as the reference writes it (bratu.jl:19, heat_2D.jl:55-58)
 __device__ __forceinline__ double lp(double c, double p, double m, double h2) { return ((p - 2.0 * c) + m) / h2; }
@@ -122,10 +123,15 @@ __global__ __launch_bounds__(kBlock) void k_jv_batch(BArgs B) {
             uu[q] = (FD && s.ok[q]) ? B.u[s.off[q]] : 0.0;
             gg[q] = (FD && SCH != 0 && s.ok[q]) ? B.un[s.off[q]] : 0.0;
         }
-        const double eu = (!FD && kind_bratu(KIND)) ? nk_exp(B.u[o]) : 0.0;       // Enzyme tangent of λ exp(u)
-        const double unc = (FD && !kind_bratu(KIND)) ? B.un[o] : 0.0;
+        constexpr bool IGN = kind_ignition(KIND);
+        const double unc = ((FD && !kind_bratu(KIND)) || (IGN && SCH == 1)) ? B.un[o] : 0.0;
+        // Enzyme tangent of λ exp(u); the ignition Midpoint tangent exponentiates m = α u_n + (1 - α) u
+        const double eu = (!FD && (kind_bratu(KIND) || IGN))
+                              ? nk_exp((IGN && SCH == 1) ? B.alpha * unc + (1.0 - B.alpha) * B.u[o] : B.u[o])
+                              : 0.0;
         const double f0 = FD ? B.F0[o] : 0.0;
         const double lsumg = (FD && SCH == 2) ? lsum_of<DIM>(B, gg) : 0.0;  // G_Trapezoid!'s du(u_n)
+        const double fg = (FD && IGN && SCH == 2) ? B.a * lsumg + B.lam * nk_exp(unc) : 0.0;  // the ignition f(u_n)
         for (int b = 0; b < B.nb; ++b) {
             const double* __restrict__ v = B.v[b];
             const double eps = B.eps[b];
@@ -147,6 +153,14 @@ __global__ __launch_bounds__(kBlock) void k_jv_batch(BArgs B) {
             if constexpr (kind_bratu(KIND)) {
                 if constexpr (FD) r = ((lsum + B.lam * nk_exp(c)) - f0) / eps;
                 else r = lsum + B.lam * (eu * c);
+            } else if constexpr (IGN) {  // f(w) = a L(w) + λ exp(w) under the scheme (nk_stencil.hpp's point_value)
+                if constexpr (!FD) {
+                    r = (SCH == 2 ? B.dt / 2.0 : B.dt) * (B.a * lsum + B.lam * (eu * c)) - xc;
+                } else {
+                    const double fw = B.a * lsum + B.lam * nk_exp(c);
+                    const double g = SCH == 2 ? (unc + (B.dt / 2.0) * (fg + fw)) - xc : (unc + B.dt * fw) - xc;
+                    r = (g - f0) / eps;
+                }
             } else if constexpr (!FD) {
                 r = (SCH == 2 ? B.dt / 2.0 : B.dt) * (B.a * lsum) - xc;
             } else {
@@ -264,9 +278,9 @@ int launch_jv_batch(nk_ctx* c, const nk_problem* p, int nb, double* const* out, 
     B.n = g.n; B.nx = p->nx; B.ny = p->ny; B.nz = p->nz;
     B.hx2 = p->hx * p->hx; B.hy2 = p->hy * p->hy; B.hz2 = p->hz * p->hz;
     B.lam = p->lambda; B.a = p->a; B.dt = p->dt; B.alpha = p->alpha;
-    const bool heat = nk_is_heat(p->kind), fd = mode == MODE_JFD;
+    const bool heat = nk_is_heat(p->kind), un = nk_has_un(p->kind), fd = mode == MODE_JFD;
     // algorithmic bytes: per point u / F0 / u_n once, each v read and each product written
-    const double words = 2.0 * nb + (fd ? 2.0 + (heat ? 1.0 : 0.0) : (heat ? 0.0 : 1.0));
+    const double words = 2.0 * nb + (fd ? 2.0 + (un ? 1.0 : 0.0) : (heat ? 0.0 : 1.0) + (p->kind == NK_IGNITION2D_MIDPOINT ? 1.0 : 0.0));
     const int grid = batch_grid(g.n);
     hipStream_t s = c->stream;
     const int kind = p->kind;
@@ -281,6 +295,9 @@ int launch_jv_batch(nk_ctx* c, const nk_problem* p, int nb, double* const* out, 
         case NK_HEAT2D_TRAPEZOID: go_batch<NK_HEAT2D_TRAPEZOID>(B, mode, grid, s); break;
         case NK_HEAT3D_TRAPEZOID: go_batch<NK_HEAT3D_TRAPEZOID>(B, mode, grid, s); break;
         case NK_BRATU3D: go_batch<NK_BRATU3D>(B, mode, grid, s); break;
+        case NK_IGNITION2D_EULER: go_batch<NK_IGNITION2D_EULER>(B, mode, grid, s); break;
+        case NK_IGNITION2D_MIDPOINT: go_batch<NK_IGNITION2D_MIDPOINT>(B, mode, grid, s); break;
+        case NK_IGNITION2D_TRAPEZOID: go_batch<NK_IGNITION2D_TRAPEZOID>(B, mode, grid, s); break;
         default: break;  // (geometry has refused every other kind)
         }
     });

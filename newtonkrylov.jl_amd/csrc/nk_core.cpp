@@ -40,6 +40,14 @@ int geometry(nk_ctx* c, const nk_problem* p, Geo* g) {
         if (c && c->nranks > 1) return fail(c, NK_E_ARG, "3D Bratu runs on one rank (z-slabs and 3D blocks are not implemented for it)");
         g->dim = 3; g->plane = p->nx * p->ny; g->nplanes = p->nz;
         break;
+    case NK_IGNITION2D_EULER:
+    case NK_IGNITION2D_MIDPOINT:
+    case NK_IGNITION2D_TRAPEZOID:
+        if (p->nz != 1) return fail(c, NK_E_ARG, "2D problem needs nz = 1");
+        if (p->bc == NK_BC_PERIODIC) return fail(c, NK_E_ARG, "the ignition kinds have bc_zero! only (periodic boundaries are not implemented for them)");
+        if (c && c->nranks > 1) return fail(c, NK_E_ARG, "the ignition kinds run on one rank (slabs are not implemented for them)");
+        g->dim = 2; g->plane = p->nx; g->nplanes = p->ny;
+        break;
     case NK_USER1D:
     case NK_USER2D:
     case NK_USER3D:
@@ -65,7 +73,7 @@ int geometry(nk_ctx* c, const nk_problem* p, Geo* g) {
     } else if (p->bc != NK_BC_ZERO) {
         return fail(c, NK_E_ARG, "unknown boundary condition");
     }
-    if (nk_is_heat(p->kind) && !p->un) return fail(c, NK_E_ARG, "heat problem needs u_n");
+    if (nk_has_un(p->kind) && !p->un) return fail(c, NK_E_ARG, nk_is_heat(p->kind) ? "heat problem needs u_n" : "ignition problem needs u_n");
     if (g->dim == 3 && c && c->px * c->py > 1) {  // 3D blocks (nk_dist_grid)
         if (p->bc == NK_BC_PERIODIC) return fail(c, NK_E_ARG, "3D blocks: bc_zero! only (periodic problems use z-slabs)");
         if (nk_is_user(p->kind)) return fail(c, NK_E_ARG, "3D blocks: built-in residuals only (user residuals use z-slabs)");

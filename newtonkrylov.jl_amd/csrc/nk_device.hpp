@@ -37,6 +37,9 @@ hipError_t stencil_bind_mb_6(const MbInfo& m);
 hipError_t stencil_bind_mb_7(const MbInfo& m);
 hipError_t stencil_bind_mb_8(const MbInfo& m);
 hipError_t stencil_bind_mb_9(const MbInfo& m);
+hipError_t stencil_bind_mb_20(const MbInfo& m);
+hipError_t stencil_bind_mb_21(const MbInfo& m);
+hipError_t stencil_bind_mb_22(const MbInfo& m);
 
 typedef double dx2 __attribute__((ext_vector_type(2)));  // 16-B streaming element
 

@@ -605,11 +605,14 @@ Halo halo_form(nk_ctx* c, const StencilIn& in, const Geo& g, const StPlan& P, bo
 // algorithmic (compulsory) bytes per launch, for the instantiation the dispatch launched (StInst: an
 // F0R kernel reads no F0)
 double st_bytes(const StencilIn& in, int64_t n, const StInst& st) {
-    const bool heat = nk_is_heat(in.p->kind);
+    // u_n: the implicit schemes; u in the exact tangent: the kinds with λ exp(u) (the ignition Midpoint tangent
+    // exponentiates α u_n + (1 - α) u: u_n as well)
+    const int kind = in.p->kind;
+    const bool un = nk_has_un(kind), heat = nk_is_heat(kind);
     int words = 1;  // out
-    if (in.mode == MODE_RES) words += 1 + (heat ? 1 : 0);
-    else if (in.mode == MODE_JEXACT) words += 1 + (heat ? 0 : 1);
-    else words += 3 + (heat ? 1 : 0) - (st.f0r ? 1 : 0);
+    if (in.mode == MODE_RES) words += 1 + (un ? 1 : 0);
+    else if (in.mode == MODE_JEXACT) words += 1 + (heat ? 0 : 1) + (kind == NK_IGNITION2D_MIDPOINT ? 1 : 0);
+    else words += 3 + (un ? 1 : 0) - (st.f0r ? 1 : 0);
     if (in.epi == EPI_RESID || (in.epi == EPI_DOT && in.aux)) words += 1;
     if (in.vout) words += 1;  // fused kdivcopy!: V_k is written
     return 8.0 * words * (double)n;
@@ -644,8 +647,13 @@ int launch_stencil_ex(nk_ctx* c, const StencilIn& in, Red* red, int rows_overrid
         knobs.ymarch = 0;
         fast &= ~524288;
     }
+    if (nk_is_ignition(p->kind)) {  // the VEC 1 / 2 row march is the kinds' only kernel (no VEC 4, no one-shot tiles)
+        knobs.vec_pref = 2;
+        knobs.oneshot = 0;
+        fast &= ~(4 | 8192 | 16384 | 32768 | 131072);
+    }
     const StPlan P = st_plan(StShape{g.dim, p->nx, p->ny, p->nz, per, blk, in.mode, nk_is_heat(p->kind), nk_scheme(p->kind),
-                                     vstore, in.aux != nullptr, rows_override, fast, in.f0r},
+                                     vstore, in.aux != nullptr, rows_override, fast, in.f0r && st_kind_f0r(p->kind)},
                              knobs);
     KArgs A{};
     A.out = in.out; A.u = in.u; A.v = in.v; A.F0 = in.F0; A.un = p->un; A.aux = in.aux;
@@ -725,6 +733,9 @@ int launch_stencil_ex(nk_ctx* c, const StencilIn& in, Red* red, int rows_overrid
         case NK_HEAT2D_TRAPEZOID: st = stencil_kind_7(A, mode, epi, vec, grid, s, per); break;
         case NK_HEAT3D_TRAPEZOID: st = stencil_kind_8(A, mode, epi, vec, grid, s, per); break;
         case NK_BRATU3D: st = stencil_kind_9(A, mode, epi, vec, grid, s, false); break;
+        case NK_IGNITION2D_EULER: st = stencil_kind_20(A, mode, epi, vec, grid, s, false); break;
+        case NK_IGNITION2D_MIDPOINT: st = stencil_kind_21(A, mode, epi, vec, grid, s, false); break;
+        case NK_IGNITION2D_TRAPEZOID: st = stencil_kind_22(A, mode, epi, vec, grid, s, false); break;
         default: break;  // (geometry has refused every other kind)
         }
         if (A.group > 1) {  // one-shot tiles: the group sums in tile order, as the next kernel's partials

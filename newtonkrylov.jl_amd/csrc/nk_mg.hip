@@ -245,6 +245,16 @@ __global__ __launch_bounds__(kBlock) void k_mg_prolong_m(MgLv Lf, MgLv Lc, int l
     }
 }
 // set-up: diag = dsum + s (dsum = Σ_a -2 c_a, summed in axis order on the host) and 1 / diag
+// the ignition kinds' s_0 (nk_mg_set_jacobian): the argument m = α u_n + (1 - α) u of G_Midpoint!'s exp, mixed as the
+// stencils mix it, and s = coef exp(.) - 1 in place on the exponentials
+__global__ __launch_bounds__(kBlock) void k_mg_ign_mix(int n, double alpha, const double* __restrict__ un, const double* __restrict__ u,
+                                                      double* __restrict__ m) {
+    NK_CHUNKED(i, n) m[i] = alpha * un[i] + (1.0 - alpha) * u[i];
+}
+__global__ __launch_bounds__(kBlock) void k_mg_ign_s(int n, double coef, double* __restrict__ s) {
+    NK_CHUNKED(i, n) s[i] = coef * s[i] - 1.0;
+}
+
 __global__ __launch_bounds__(kBlock) void k_mg_diag(int n, double dsum, const double* __restrict__ s, double* __restrict__ dg,
                                                    double* __restrict__ idg) {
     NK_CHUNKED(i, n) {
@@ -571,7 +581,7 @@ int mg_free(nk_mg* m) {
     return NK_OK;
 }
 
-bool mg_kind_ok(int kind) { return (kind >= NK_BRATU1D && kind <= NK_HEAT3D_TRAPEZOID) || kind == NK_BRATU3D; }
+bool mg_kind_ok(int kind) { return (kind >= NK_BRATU1D && kind <= NK_HEAT3D_TRAPEZOID) || kind == NK_BRATU3D || nk_is_ignition(kind); }
 
 // slabs: pos[l] / neg[l] of this rank's rows -> of the whole level, through the context's cross-rank sum.  Every rank
 // adds 1 (positive) + 64 (negative) per level (at most kMbRanks = 32 < 64 ranks: no carry), four levels of 12 bits to
@@ -730,6 +740,8 @@ int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int6
     if (dist && p->kind == NK_BRATU1D) return fail(c, NK_E_ARG, "multigrid: 1D kinds are not implemented on a distributed context");
     if (dist && p->kind == NK_BRATU3D)
         return fail(c, NK_E_ARG, "multigrid: NK_BRATU3D runs on one rank (a distributed context is not implemented for it)");
+    if (dist && nk_is_ignition(p->kind))
+        return fail(c, NK_E_ARG, "multigrid: the ignition kinds run on one rank (a distributed context is not implemented for them)");
     if (dist && given)
         return fail(c, NK_E_ARG, "multigrid: a level list (semicoarsening) is not implemented on a distributed context");
     Geo g;
@@ -891,7 +903,27 @@ int nk_mg_set_jacobian(nk_mg* m, const nk_problem* p, const double* u) {
         return fail(c, NK_E_ARG, "multigrid: the problem does not match the hierarchy's (kind, grid, spacings, bc_zero!)");
     double k[3] = {0.0, 0.0, 0.0};
     const int64_t n = m->lv[0].n;
-    if (nk_is_heat(p->kind)) {
+    if (nk_is_ignition(p->kind)) {
+        // J = θ Δt (a L + λ diag(exp(m))) - I: k_a = θ a Δt as for the heat kinds, s = θ Δt λ exp(m) - 1 with m = u
+        // (G_Midpoint!: α u_n + (1 - α) u).  s turns positive where θ Δt λ exp(m) > 1 (near blow-up): the diagonal then
+        // changes sign on some level and mg_setup truncates the hierarchy there, as for Bratu above the fold
+        const int sch = nk_scheme(p->kind);
+        const double theta = sch == 1 ? 1.0 - p->alpha : (sch == 2 ? 0.5 : 1.0);
+        if (!p->un) return fail(c, NK_E_ARG, "ignition problem needs u_n");
+        for (int a = 0; a < m->dim; ++a) k[a] = theta * p->a * p->dt;
+        const double* arg = u;
+        if (sch == 1) {  // (a level-0 work vector holds m: no cycle runs during the setup)
+            NK_TRY(launch(c, "mg_setup_mix", 24.0 * n, [&] {
+                hipLaunchKernelGGL(k_mg_ign_mix, dim3(wide_blocks(n)), dim3(kBlock), 0, c->stream, (int)n, p->alpha, p->un, u, m->xa[0]);
+            }));
+            arg = m->xa[0];
+        }
+        NK_TRY(launch_exp(c, n, m->s[0], arg));  // the stencils' own correctly rounded exp
+        const double coef = (sch == 2 ? p->dt / 2.0 : p->dt) * (sch == 1 ? 1.0 - p->alpha : 1.0) * p->lambda;
+        NK_TRY(launch(c, "mg_setup_s", 16.0 * n, [&] {
+            hipLaunchKernelGGL(k_mg_ign_s, dim3(wide_blocks(n)), dim3(kBlock), 0, c->stream, (int)n, coef, m->s[0]);
+        }));
+    } else if (nk_is_heat(p->kind)) {
         const int sch = nk_scheme(p->kind);
         const double theta = sch == 1 ? 1.0 - p->alpha : (sch == 2 ? 0.5 : 1.0);
         for (int a = 0; a < m->dim; ++a) k[a] = theta * p->a * p->dt;

@@ -57,9 +57,10 @@ __global__ __launch_bounds__(kBlock) void k_jdiag(KArgs A, double* __restrict__ 
         double lsum = lapk(A, c, 0.0, 0.0, A.hx2, A.ihx2);
         if (DIM >= 2) lsum = lsum + lapk(A, c, 0.0, 0.0, A.hy2, A.ihy2);
         if (DIM == 3) lsum = lsum + lapk(A, c, 0.0, 0.0, A.hz2, A.ihz2);
-        const double uc = kind_bratu(KIND) ? A.u[i] : 0.0;
+        const double uc = kind_has_exp(KIND) ? A.u[i] : 0.0;
+        const double unc = KIND == NK_IGNITION2D_MIDPOINT ? A.un[i] : 0.0;  // its tangent exponentiates α u_n + (1 - α) u
         bool rare_ = false;
-        const double d = point_value<KIND, MODE_JEXACT>(A, c, lsum, uc, 0.0, 0.0, 1.0, 0.0, &NKX_T[0][0], rare_);
+        const double d = point_value<KIND, MODE_JEXACT>(A, c, lsum, uc, unc, 0.0, 1.0, 0.0, &NKX_T[0][0], rare_);
         out[i] = recip ? 1.0 / d : d;
     }
 }
@@ -87,6 +88,7 @@ int launch_diag_apply(nk_ctx* c, int64_t n, double* z, const double* d, const do
 int launch_jdiag(nk_ctx* c, const nk_problem* p, double* out, const double* u, int recip) {
     KArgs A{};
     A.u = u;
+    A.un = p->un;
     A.nx = p->nx; A.ny = p->ny; A.nz = p->nz;
     A.hx2 = p->hx * p->hx; A.hy2 = p->hy * p->hy; A.hz2 = p->hz * p->hz;
     A.lam = p->lambda; A.a = p->a; A.dt = p->dt; A.alpha = p->alpha;
@@ -104,6 +106,9 @@ int launch_jdiag(nk_ctx* c, const nk_problem* p, double* out, const double* u, i
         case NK_HEAT3D_TRAPEZOID: NK_JDIAG(NK_HEAT3D_TRAPEZOID, 3); break;
         case NK_HEAT3D_EULER: NK_JDIAG(NK_HEAT3D_EULER, 3); break;
         case NK_BRATU3D: NK_JDIAG(NK_BRATU3D, 3); break;
+        case NK_IGNITION2D_EULER: NK_JDIAG(NK_IGNITION2D_EULER, 2); break;
+        case NK_IGNITION2D_MIDPOINT: NK_JDIAG(NK_IGNITION2D_MIDPOINT, 2); break;
+        case NK_IGNITION2D_TRAPEZOID: NK_JDIAG(NK_IGNITION2D_TRAPEZOID, 2); break;
         default: break;  // (geometry has refused every other kind)
         }
     });
@@ -334,12 +339,13 @@ __global__ __launch_bounds__(64) void k_ilu0_pipe(IluPipe P) {
 
 // off-diagonal entry of J along one axis: the exact tangent at point i of the unit vector on its
 // neighbour (the entry collect(J) holds): lap = f / h^2 with f = 1 ((1 - α) for G_Midpoint!), the
-// other axes add +0, Bratu adds λ (e^u · 0) = +0, heat: (Δt or Δt/2) (a lap) - 0
+// other axes add +0, Bratu adds λ (e^u · 0) = +0, heat: (Δt or Δt/2) (a lap) - 0; the ignition kinds: the heat kind's
+// value, since a lap + λ (e^m · 0) = a lap + 0
 double ilu_offdiag(const nk_problem* p, double h) {
-    const int sch = nk_is_heat(p->kind) ? nk_scheme(p->kind) : 0;
+    const int sch = nk_has_un(p->kind) ? nk_scheme(p->kind) : 0;
     const double f = sch == 1 ? (1.0 - p->alpha) * 1.0 : 1.0;
     const double lsum = ((f - 2.0 * 0.0) + 0.0) / (h * h);
-    if (!nk_is_heat(p->kind)) return lsum;
+    if (!nk_has_un(p->kind)) return lsum;
     return (sch == 2 ? p->dt / 2.0 : p->dt) * (p->a * lsum) - 0.0;
 }
 

@@ -79,16 +79,20 @@ NK_ST_DECL(6)
 NK_ST_DECL(7)
 NK_ST_DECL(8)
 NK_ST_DECL(9)
+NK_ST_DECL(20)
+NK_ST_DECL(21)
+NK_ST_DECL(22)
 #undef NK_ST_DECL
 
 namespace {
 
-// implicit.jl scheme of a heat kind: 0 G_Euler! (and the Bratu kinds, NK_BRATU3D included), 1 G_Midpoint!, 2 G_Trapezoid!
+// implicit.jl scheme of a heat or ignition kind: 0 G_Euler! (and the Bratu kinds, NK_BRATU3D included), 1 G_Midpoint!,
+// 2 G_Trapezoid!
 template <int KIND>
 constexpr int scheme_of() {
-    return (KIND == NK_HEAT2D_MIDPOINT || KIND == NK_HEAT3D_MIDPOINT)
+    return (KIND == NK_HEAT2D_MIDPOINT || KIND == NK_HEAT3D_MIDPOINT || KIND == NK_IGNITION2D_MIDPOINT)
                ? 1
-               : ((KIND == NK_HEAT2D_TRAPEZOID || KIND == NK_HEAT3D_TRAPEZOID) ? 2 : 0);
+               : ((KIND == NK_HEAT2D_TRAPEZOID || KIND == NK_HEAT3D_TRAPEZOID || KIND == NK_IGNITION2D_TRAPEZOID) ? 2 : 0);
 }
 template <int KIND>
 constexpr bool heat_kind() {  // (NK_BRATU3D = 9 lies beyond the heat range)
@@ -196,6 +200,12 @@ __device__ __forceinline__ void storevec(double* __restrict__ p, int64_t o, cons
 }
 
 constexpr bool kind_bratu(int k) { return k == NK_BRATU1D || k == NK_BRATU2D || k == NK_BRATU3D; }
+// the ignition kinds: an implicit scheme composed with f(u) = a Δu + λ exp(u) -- 2D, one rank, bc_zero!
+constexpr bool kind_ignition(int k) { return k >= NK_IGNITION2D_EULER && k <= NK_IGNITION2D_TRAPEZOID; }
+// every point evaluates exp: the table in LDS (NK_EXP_LDS) and the per-lane exact phase (XM = 2)
+constexpr bool kind_has_exp(int k) { return kind_bratu(k) || kind_ignition(k); }
+// the kind carries u_n (an implicit scheme, whatever f it is composed with)
+constexpr bool kind_has_un(int k) { return (k >= NK_HEAT2D_EULER && k <= NK_HEAT3D_TRAPEZOID) || kind_ignition(k); }
 // A/B only (-DNK_ST_KEEP_VDIV): keep the runtime v / h test in every instantiation (round 3's form, where
 // the instances without the fused normalisation evaluated the division and discarded it)
 #ifdef NK_ST_KEEP_VDIV
@@ -219,8 +229,18 @@ constexpr bool kKeepVdiv = false;
 #ifndef NK_ST2D_HEAT_CAP  // A/B: occupancy caps for the trapezoid kernels (no gain: profiles/r04/ab_trapezoid_caps.log)
 #define NK_ST2D_HEAT_CAP 0
 #endif
+// Waves per SIMD the ignition kinds' k_st2d instances (the u_n rows of the heat march plus the exp's registers) are
+// allocated for: 3 (<= 168 VGPRs), no scratch in any instance (the table in DESIGN.md §13).  Unconstrained they take 92 to
+// 169 VGPRs -- the same code everywhere but in the Trapezoid FD Jv + dot with V_k stored, whose 169 would run at 2 waves.
+// The Bratu march's 4-wave cap (<= 128) spills 16 to 176 B per lane in 34 of the 108 instances: it measured about 10 %
+// faster on the Euler and Midpoint FD Jv at 4096^2 and neutral elsewhere (profiles/ignition/), but these kinds ship
+// without scratch.  NK_ST2D_IGN_WPE: a `make variant` define for that A/B.
+#ifndef NK_ST2D_IGN_WPE
+#define NK_ST2D_IGN_WPE 3
+#endif
 constexpr int st2d_wpe(int kind, int mode, bool f0r) {
-    return kind_bratu(kind) ? NK_ST2D_BRATU_WPE
+    return kind_ignition(kind) ? NK_ST2D_IGN_WPE
+           : kind_bratu(kind) ? NK_ST2D_BRATU_WPE
                             : ((NK_ST2D_HEAT_CAP && kind == NK_HEAT2D_TRAPEZOID)
                                    ? (mode == MODE_RES ? 6 : (f0r ? 4 : 1))
                                    : 1);
@@ -230,9 +250,9 @@ constexpr int st2d_wpe(int kind, int mode, bool f0r) {
 // kinds, where every point evaluates exp: read with ds_read, its lookups never wait behind the rows the
 // march keeps in flight (a global-memory table would share their in-order vmcnt).  Declares `et`.
 #define NK_EXP_LDS(KIND)                                                                              \
-    __shared__ double et_lds[kind_bratu(KIND) ? 256 : 2];                                             \
+    __shared__ double et_lds[kind_has_exp(KIND) ? 256 : 2];                                           \
     const double* const et = et_lds;                                                                  \
-    if constexpr (kind_bratu(KIND)) {                                                                 \
+    if constexpr (kind_has_exp(KIND)) {                                                               \
         for (int i_ = threadIdx.x; i_ < 256; i_ += blockDim.x) et_lds[i_] = (&NKX_T[0][0])[i_];        \
         __syncthreads();                                                                              \
     }
@@ -244,12 +264,39 @@ constexpr int st2d_wpe(int kind, int mode, bool f0r) {
 //   Euler      (u_n + Δt du(w)) - w                      tangent  Δt (a lap(v)) - v
 //   Midpoint   (u_n + Δt du(α u_n + (1-α) w)) - w        tangent  Δt (a lap((1-α) v)) - v
 //   Trapezoid  (u_n + (Δt/2) (du(u_n) + du(w))) - w      tangent  (Δt/2) (a lap(v)) - v
-// et: the exp table (nk_exp.h's NKX_T) in LDS for the Bratu kinds (NK_EXP_LDS), unused otherwise.
+// et: the exp table (nk_exp.h's NKX_T) in LDS for the Bratu and ignition kinds (NK_EXP_LDS), unused otherwise.
 // XM = 1: the exp's fast phase only -- a lane it does not settle sets `rare` (its value is then not the
 // correctly rounded one, and the caller recomputes: k_st2d's two-pass march); XM = 0: nk_exp_t itself.
 template <int KIND, int MODE, int XM = 0>
 __device__ __forceinline__ double point_value(const KArgs& A, double c, double lsum, double uc, double unc, double f0c,
                                               double xc, double lsumg, const double* et, bool& rare) {
+    // the library's correctly rounded exp, in the phase form the caller's march asks for (the kinds with an exp term)
+    auto ex = [&](double x) {
+#ifdef NK_KBENCH
+        if (A.fast & (1 << 22)) {  // kbench diagnosis only: the fast phase's value, no rounding test acted on
+            double y;
+            (void)nkx_exp_fast(x, et, &y);
+            return y;
+        }
+#endif
+// NK_ST_EXP_DIAG (product variant builds for diagnosis only -- wrong answers): 1 the platform exp, 2 no exp,
+// the march's floor without the correctly rounded exp (profiles/r05/ab_expdiag.log)
+#if defined(NK_ST_EXP_DIAG) && NK_ST_EXP_DIAG == 1
+        return exp(x);
+#elif defined(NK_ST_EXP_DIAG) && NK_ST_EXP_DIAG == 2  // no exp at all: the march's cost without it
+        return x;
+#endif
+        if constexpr (XM == 1) {
+            double y;
+            if (!nkx_exp_fast(x, et, &y)) rare = true;
+            return y;
+        } else if constexpr (XM == 2) {
+            return nk_exp_lane(x, et);
+        } else {
+            return nk_exp_t(x, et);
+        }
+    };
+    (void)ex;
     if constexpr (kind_bratu(KIND)) {
 #ifdef NK_KBENCH
         if (A.fast & (1 << 20)) {  // kbench A/B only: the platform (ocml) exp, <= 1 ulp off the correctly rounded one
@@ -258,33 +305,23 @@ __device__ __forceinline__ double point_value(const KArgs& A, double c, double l
             return MODE == MODE_JFD ? fdq(A, r, f0c) : r;
         }
 #endif
-        auto ex = [&](double x) {
-#ifdef NK_KBENCH
-            if (A.fast & (1 << 22)) {  // kbench diagnosis only: the fast phase's value, no rounding test acted on
-                double y;
-                (void)nkx_exp_fast(x, et, &y);
-                return y;
-            }
-#endif
-// NK_ST_EXP_DIAG (product variant builds for diagnosis only -- wrong answers): 1 the platform exp, 2 no exp,
-// the march's floor without the correctly rounded exp (profiles/r05/ab_expdiag.log)
-#if defined(NK_ST_EXP_DIAG) && NK_ST_EXP_DIAG == 1
-            return exp(x);
-#elif defined(NK_ST_EXP_DIAG) && NK_ST_EXP_DIAG == 2  // no exp at all: the march's cost without it
-            return x;
-#endif
-            if constexpr (XM == 1) {
-                double y;
-                if (!nkx_exp_fast(x, et, &y)) rare = true;
-                return y;
-            } else if constexpr (XM == 2) {
-                return nk_exp_lane(x, et);
-            } else {
-                return nk_exp_t(x, et);
-            }
-        };
         if (MODE == MODE_JEXACT) return lsum + A.lam * (ex(uc) * c);  // Enzyme tangent of λ exp(u)
         const double r = lsum + A.lam * ex(c);
+        return MODE == MODE_JFD ? fdq(A, r, f0c) : r;
+    } else if constexpr (kind_ignition(KIND)) {
+        // G ∘ f with f(w) = a L(w) + λ exp(w) (diffusion!'s a * (...) plus Bratu's λ * exp(u)), nothing contracted:
+        //   Euler      (u_n + Δt f(w)) - w                       tangent  Δt (a L(v) + λ (exp(u) v)) - v
+        //   Midpoint   (u_n + Δt f(m)) - w, m = α u_n + (1-α) w  tangent  Δt (a L(c) + λ (exp(m) c)) - v, c = (1-α) v
+        //   Trapezoid  (u_n + (Δt/2) (f(u_n) + f(w))) - w        tangent  (Δt/2) (a L(v) + λ (exp(u) v)) - v
+        // c = the stencil field's centre (m for Midpoint), uc / unc = the centres of u / u_n, xc the "- w" term
+        constexpr int SCH = scheme_of<KIND>();
+        if (MODE == MODE_JEXACT) {
+            const double m = SCH == 1 ? A.alpha * unc + (1.0 - A.alpha) * uc : uc;
+            return (SCH == 2 ? A.dt / 2.0 : A.dt) * (A.a * lsum + A.lam * (ex(m) * c)) - xc;
+        }
+        const double fw = A.a * lsum + A.lam * ex(c);
+        const double r = SCH == 2 ? (unc + (A.dt / 2.0) * ((A.a * lsumg + A.lam * ex(unc)) + fw)) - xc
+                                  : (unc + A.dt * fw) - xc;
         return MODE == MODE_JFD ? fdq(A, r, f0c) : r;
     } else {  // implicit.jl:8-37
         constexpr int SCH = scheme_of<KIND>();

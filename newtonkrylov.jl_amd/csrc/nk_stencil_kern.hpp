@@ -54,8 +54,11 @@ void k_st2d(KArgs A0) {
             }
         }
     }
-    constexpr bool kU = MODE == MODE_JEXACT && KIND == NK_BRATU2D;
-    constexpr bool kUn = KIND == NK_HEAT2D_EULER && MODE != MODE_JEXACT;
+    // centre-only operands: u for the tangent of λ exp(u) (the ignition Midpoint tangent exponentiates
+    // m = α u_n + (1-α) u: the centre of u_n as well); u_n where the scheme carries no u_n rows (kG)
+    constexpr bool kU = MODE == MODE_JEXACT && (KIND == NK_BRATU2D || kind_ignition(KIND));
+    constexpr bool kUn = ((KIND == NK_HEAT2D_EULER || KIND == NK_IGNITION2D_EULER) && MODE != MODE_JEXACT) ||
+                         (KIND == NK_IGNITION2D_MIDPOINT && MODE == MODE_JEXACT);
     constexpr bool kF0 = MODE == MODE_JFD && !F0R;
     constexpr bool kR = MODE == MODE_JFD && F0R;  // the u field, cooked as the residual kernel cooks it
     constexpr bool kAx = EPI == EPI_DOT || EPI == EPI_DOTV || EPI == EPI_RESID;
@@ -176,7 +179,7 @@ void k_st2d(KArgs A0) {
     }
     return rare;
     };
-    if constexpr (kind_bratu(KIND)) {
+    if constexpr (kind_has_exp(KIND)) {
 #if NK_ST2D_BRATU_XM == 2
         (void)march(std::integral_constant<int, 2>{});
 #else
@@ -716,15 +719,19 @@ namespace {
 template <int KIND, int MODE, int EPI>
 StInst go_stencil(const KArgs& A, int vec, int grid, hipStream_t s, bool per) {
     constexpr bool k2d = KIND == NK_BRATU2D || KIND == NK_HEAT2D_EULER || KIND == NK_HEAT2D_MIDPOINT ||
-                         KIND == NK_HEAT2D_TRAPEZOID;
+                         KIND == NK_HEAT2D_TRAPEZOID || kind_ignition(KIND);
     if constexpr (KIND == NK_BRATU1D) {
         return go_st1d<MODE, EPI>(A, grid, s);
     } else if constexpr (k2d) {
 #ifdef NK_KBENCH
         // one-shot LDS tiles (k_st2t, kernel-variant build only: NK_ST_ONESHOT / fast bits)
-        if (A.tile2) return go_st2t<KIND, MODE, EPI>(A, vec, grid, s, per);
+        if constexpr (!kind_ignition(KIND)) {  // (the ignition kinds: the row march only)
+            if (A.tile2) return go_st2t<KIND, MODE, EPI>(A, vec, grid, s, per);
+        }
 #endif
-        if constexpr (MODE == MODE_JFD) {  // F0 recomputed from u (KArgs::f0r), VEC <= 2
+        // the ignition kinds have the plain row march only: no F0R, no periodic instance (st_plan never plans F0R
+        // for them, geometry refuses bc_periodic!)
+        if constexpr (MODE == MODE_JFD && !kind_ignition(KIND)) {  // F0 recomputed from u (KArgs::f0r), VEC <= 2
             if (A.f0r && vec <= 2) {
                 if constexpr (heat_kind<KIND>()) {  // bc_periodic! (heat only) with F(u) recomputed
                     if (per) return vec == 2 ? go_st2d<KIND, MODE, EPI, 2, true, true>(A, grid, s)
@@ -739,7 +746,9 @@ StInst go_stencil(const KArgs& A, int vec, int grid, hipStream_t s, bool per) {
                                      : go_st2d<KIND, MODE, EPI, 1, true>(A, grid, s);
         }
 #ifdef NK_KBENCH
-        if (vec == 4) return go_st2d<KIND, MODE, EPI, 4>(A, grid, s);
+        if constexpr (!kind_ignition(KIND)) {
+            if (vec == 4) return go_st2d<KIND, MODE, EPI, 4>(A, grid, s);
+        }
 #endif
         return vec == 2 ? go_st2d<KIND, MODE, EPI, 2>(A, grid, s) : go_st2d<KIND, MODE, EPI, 1>(A, grid, s);
     } else {

@@ -20,6 +20,7 @@ const NK_HEAT2D_MIDPOINT, NK_HEAT3D_MIDPOINT, NK_HEAT2D_TRAPEZOID, NK_HEAT3D_TRA
 const NK_BRATU3D = Int32(9)
 const NK_BC_ZERO, NK_BC_PERIODIC = Int32(0), Int32(1)
 const NK_USER1D, NK_USER2D, NK_USER3D = Int32(16), Int32(17), Int32(18)
+const NK_IGNITION2D_EULER, NK_IGNITION2D_MIDPOINT, NK_IGNITION2D_TRAPEZOID = Int32(20), Int32(21), Int32(22)
 const NK_JV_EXACT, NK_JV_FD = Int32(0), Int32(1)
 const NK_ALGO_GMRES, NK_ALGO_CG, NK_ALGO_FGMRES, NK_ALGO_MINRES = Int32(0), Int32(1), Int32(2), Int32(3)
 
@@ -216,11 +217,17 @@ const heat2d_trapezoid! = HipResidual{:heat2d_trapezoid}()
 const heat3d_euler! = HipResidual{:heat3d}()
 const heat3d_midpoint! = HipResidual{:heat3d_midpoint}()
 const heat3d_trapezoid! = HipResidual{:heat3d_trapezoid}()
+# G ∘ f!, f(u) = a Δu + λ exp(u) (solid fuel ignition, DESIGN.md §13), p = (uₙ, Δt, du, (a, Δx, Δy, λ, bc_zero!), t); 2D, one rank
+const ignition2d_euler! = HipResidual{:ignition2d}()
+const ignition2d_midpoint! = HipResidual{:ignition2d_midpoint}()    # α = 0.5; HipResidual{:ignition2d_midpoint}(α = 0.3)
+const ignition2d_trapezoid! = HipResidual{:ignition2d_trapezoid}()
 
 # bc_zero! / bc_periodic! of examples/heat_2D.jl:15-38, recognised by name
 bccode(bc) = nameof(bc) === :bc_periodic! ? NK_BC_PERIODIC : NK_BC_ZERO
 const HEAT_KINDS = (heat2d = NK_HEAT2D_EULER, heat2d_midpoint = NK_HEAT2D_MIDPOINT, heat2d_trapezoid = NK_HEAT2D_TRAPEZOID,
                     heat3d = NK_HEAT3D_EULER, heat3d_midpoint = NK_HEAT3D_MIDPOINT, heat3d_trapezoid = NK_HEAT3D_TRAPEZOID)
+const IGNITION_KINDS = (ignition2d = NK_IGNITION2D_EULER, ignition2d_midpoint = NK_IGNITION2D_MIDPOINT,
+                        ignition2d_trapezoid = NK_IGNITION2D_TRAPEZOID)
 
 problem(F::HipResidual{:bratu1d}, u::HipVector, (dx, λ)) = NkProblem(NK_BRATU1D, 0, u.grid..., dx, 1, 1, λ, 0, 0, C_NULL, C_NULL, F.α)
 problem(F::HipResidual{:bratu2d}, u::HipVector, (dx, dy, λ)) = NkProblem(NK_BRATU2D, 0, u.grid..., dx, dy, 1, λ, 0, 0, C_NULL, C_NULL, F.α)
@@ -232,6 +239,14 @@ function problem(F::HipResidual{K}, u::HipVector, (un, Δt, _, fp, _t)) where {K
     a, dx, dy = fp[1], fp[2], fp[3]
     dz = three ? fp[4] : 1.0
     return NkProblem(kind, bccode(fp[end]), u.grid..., dx, dy, dz, 0, a, Δt, un.ptr, C_NULL, F.α)
+end
+const HipIgnition = Union{HipResidual{:ignition2d}, HipResidual{:ignition2d_midpoint}, HipResidual{:ignition2d_trapezoid}}
+function problem(F::HipIgnition, u::HipVector, (un, Δt, _, fp, _t))
+    K = typeof(F).parameters[1]
+    length(fp) == 5 || error("$(K): p[4] must be (a, Δx, Δy, λ, bc_zero!)")
+    bccode(fp[end]) == NK_BC_ZERO || error("$(K): bc_zero! only")
+    a, dx, dy, λ = fp[1], fp[2], fp[3], fp[4]
+    return NkProblem(IGNITION_KINDS[K], NK_BC_ZERO, u.grid..., dx, dy, 1.0, λ, a, Δt, un.ptr, C_NULL, F.α)
 end
 
 # --------------------------------------------------------------------------- user residuals (NK_USER*)

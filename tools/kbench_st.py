@@ -32,14 +32,15 @@ lib = ah.load()
 lib.nkb_stencil_kind.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.POINTER(C.c_double)]
 NAME = {2: "bratu2d", 3: "heat2d euler", 4: "heat3d euler", 5: "heat2d midpoint", 6: "heat3d midpoint",
-        7: "heat2d trapezoid", 8: "heat3d trapezoid"}
+        7: "heat2d trapezoid", 8: "heat3d trapezoid", 20: "ignition2d euler", 21: "ignition2d midpoint",
+        22: "ignition2d trapezoid"}
 MODE = {(0, 1): "residual+norm", (2, 2): "FD Jv+dot", (1, 2): "exact Jv+dot"}
 
 
 def words(kind, mode, epi, fast=0):  # the launcher's algorithmic count (fast bit 32: F0 recomputed)
-    heat = kind >= 3
+    heat, ign = kind >= 3, kind >= 20  # (heat: carries u_n; the ignition kinds' exact tangent reads u as well, Midpoint's u_n too)
     w = 1
-    w += (1 + heat) if mode == 0 else ((1 + (not heat)) if mode == 1 else (3 + heat))
+    w += (1 + heat) if mode == 0 else ((1 + (not heat) + ign + (kind == 21)) if mode == 1 else (3 + heat))
     f0r = mode == 2 and fast & 32 and (kind in (2, 3, 5, 7) or kind == 4)
     vout = mode != 0 and epi == 2 and fast & 256  # fused normalisation: V_k stored
     return w + (1 if epi == 2 else 0) - (1 if f0r else 0) + (1 if vout else 0)
