@@ -40,20 +40,6 @@ struct BArgs {
 
 namespace {
 
-template <int KIND>
-constexpr int kind_dim() {
-    return KIND == NK_BRATU1D ? 1
-                              : ((KIND == NK_HEAT3D_EULER || KIND == NK_HEAT3D_MIDPOINT || KIND == NK_HEAT3D_TRAPEZOID || KIND == NK_BRATU3D) ? 3 : 2);
-}
-template <int KIND>
-constexpr int kind_scheme() {
-    return (KIND == NK_HEAT2D_MIDPOINT || KIND == NK_HEAT3D_MIDPOINT || KIND == NK_IGNITION2D_MIDPOINT)
-               ? 1
-               : ((KIND == NK_HEAT2D_TRAPEZOID || KIND == NK_HEAT3D_TRAPEZOID || KIND == NK_IGNITION2D_TRAPEZOID) ? 2 : 0);
-}
-constexpr bool kind_bratu(int k) { return k == NK_BRATU1D || k == NK_BRATU2D || k == NK_BRATU3D; }
-constexpr bool kind_ignition(int k) { return k >= NK_IGNITION2D_EULER && k <= NK_IGNITION2D_TRAPEZOID; }
-
 // ((p - 2c) + m) / h^2 exactly as the reference writes it (bratu.jl:19, heat_2D.jl:55-58)
 __device__ __forceinline__ double lp(double c, double p, double m, double h2) { return ((p - 2.0 * c) + m) / h2; }
 
@@ -113,7 +99,7 @@ __device__ __forceinline__ double lsum_of(const BArgs& B, const double* f) {
 // All nb products at the point o: u, F0, u_n (and their stencil values) are loaded once.
 template <int KIND, int MODE>
 __global__ __launch_bounds__(kBlock) void k_jv_batch(BArgs B) {
-    constexpr int DIM = kind_dim<KIND>(), NP = 2 * DIM + 1, SCH = kind_scheme<KIND>();
+    constexpr int DIM = kind_of(KIND).dim, NP = 2 * DIM + 1, SCH = kind_of(KIND).scheme;
     constexpr bool FD = MODE == MODE_JFD;
     for (int64_t o = (int64_t)blockIdx.x * kBlock + threadIdx.x; o < B.n; o += (int64_t)gridDim.x * kBlock) {
         const Nbrs<DIM> s = nbrs<DIM>(B, o);
@@ -123,10 +109,10 @@ __global__ __launch_bounds__(kBlock) void k_jv_batch(BArgs B) {
             uu[q] = (FD && s.ok[q]) ? B.u[s.off[q]] : 0.0;
             gg[q] = (FD && SCH != 0 && s.ok[q]) ? B.un[s.off[q]] : 0.0;
         }
-        constexpr bool IGN = kind_ignition(KIND);
-        const double unc = ((FD && !kind_bratu(KIND)) || (IGN && SCH == 1)) ? B.un[o] : 0.0;
+        constexpr bool IGN = kind_of(KIND).ignition;
+        const double unc = ((FD && !kind_of(KIND).bratu) || (IGN && SCH == 1)) ? B.un[o] : 0.0;
         // Enzyme tangent of λ exp(u); the ignition Midpoint tangent exponentiates m = α u_n + (1 - α) u
-        const double eu = (!FD && (kind_bratu(KIND) || IGN))
+        const double eu = (!FD && (kind_of(KIND).bratu || IGN))
                               ? nk_exp((IGN && SCH == 1) ? B.alpha * unc + (1.0 - B.alpha) * B.u[o] : B.u[o])
                               : 0.0;
         const double f0 = FD ? B.F0[o] : 0.0;
@@ -150,7 +136,7 @@ __global__ __launch_bounds__(kBlock) void k_jv_batch(BArgs B) {
             if (SCH != 1) xc = c;
             const double lsum = lsum_of<DIM>(B, f);
             double r;
-            if constexpr (kind_bratu(KIND)) {
+            if constexpr (kind_of(KIND).bratu) {
                 if constexpr (FD) r = ((lsum + B.lam * nk_exp(c)) - f0) / eps;
                 else r = lsum + B.lam * (eu * c);
             } else if constexpr (IGN) {  // f(w) = a L(w) + λ exp(w) under the scheme (nk_stencil.hpp's point_value)
@@ -278,29 +264,17 @@ int launch_jv_batch(nk_ctx* c, const nk_problem* p, int nb, double* const* out, 
     B.n = g.n; B.nx = p->nx; B.ny = p->ny; B.nz = p->nz;
     B.hx2 = p->hx * p->hx; B.hy2 = p->hy * p->hy; B.hz2 = p->hz * p->hz;
     B.lam = p->lambda; B.a = p->a; B.dt = p->dt; B.alpha = p->alpha;
-    const bool heat = nk_is_heat(p->kind), un = nk_has_un(p->kind), fd = mode == MODE_JFD;
+    const Kind K = kind_of(p->kind);
+    const bool fd = mode == MODE_JFD;
     // algorithmic bytes: per point u / F0 / u_n once, each v read and each product written
-    const double words = 2.0 * nb + (fd ? 2.0 + (un ? 1.0 : 0.0) : (heat ? 0.0 : 1.0) + (p->kind == NK_IGNITION2D_MIDPOINT ? 1.0 : 0.0));
+    const double words = 2.0 * nb + (fd ? 2.0 + (K.un ? 1.0 : 0.0) : (K.exp ? 1.0 : 0.0) + (jexact_reads_un(p->kind) ? 1.0 : 0.0));
     const int grid = batch_grid(g.n);
     hipStream_t s = c->stream;
-    const int kind = p->kind;
-    return launch(c, fd ? "jv_fd_batch" : "jv_exact_batch", 8.0 * words * (double)g.n, [&] {
-        switch (kind) {
-        case NK_BRATU1D: go_batch<NK_BRATU1D>(B, mode, grid, s); break;
-        case NK_BRATU2D: go_batch<NK_BRATU2D>(B, mode, grid, s); break;
-        case NK_HEAT2D_EULER: go_batch<NK_HEAT2D_EULER>(B, mode, grid, s); break;
-        case NK_HEAT3D_EULER: go_batch<NK_HEAT3D_EULER>(B, mode, grid, s); break;
-        case NK_HEAT2D_MIDPOINT: go_batch<NK_HEAT2D_MIDPOINT>(B, mode, grid, s); break;
-        case NK_HEAT3D_MIDPOINT: go_batch<NK_HEAT3D_MIDPOINT>(B, mode, grid, s); break;
-        case NK_HEAT2D_TRAPEZOID: go_batch<NK_HEAT2D_TRAPEZOID>(B, mode, grid, s); break;
-        case NK_HEAT3D_TRAPEZOID: go_batch<NK_HEAT3D_TRAPEZOID>(B, mode, grid, s); break;
-        case NK_BRATU3D: go_batch<NK_BRATU3D>(B, mode, grid, s); break;
-        case NK_IGNITION2D_EULER: go_batch<NK_IGNITION2D_EULER>(B, mode, grid, s); break;
-        case NK_IGNITION2D_MIDPOINT: go_batch<NK_IGNITION2D_MIDPOINT>(B, mode, grid, s); break;
-        case NK_IGNITION2D_TRAPEZOID: go_batch<NK_IGNITION2D_TRAPEZOID>(B, mode, grid, s); break;
-        default: break;  // (geometry has refused every other kind)
-        }
+    bool known = true;
+    const int rc = launch(c, fd ? "jv_fd_batch" : "jv_exact_batch", 8.0 * words * (double)g.n, [&] {
+        known = for_kind(p->kind, [&](auto KC) { go_batch<decltype(KC)::value>(B, mode, grid, s); });
     });
+    return known ? rc : fail(c, NK_E_ARG, "batched Jv: not a built-in stencil kind");
 }
 
 // collect(J) of a built-in stencil on one rank (exact tangent): CSC arrays, 0-based, on the host.
@@ -403,7 +377,7 @@ int collect_unit(nk_ctx* c, const nk_problem* p, const double* u, int transpose,
     Geo g;
     NK_TRY(geometry(c, p, &g));
     if (g.n > 8192) return fail(c, NK_E_ARG, "collect(J) by unit probing is limited to n <= 8192 points");
-    const bool user = nk_is_user(p->kind);
+    const bool user = kind_of(p->kind).user;
     nk_problem geo = *p;
     std::vector<double*> pv(kMaxBatch, nullptr), po(kMaxBatch, nullptr);
     int rc = NK_OK;
@@ -468,10 +442,10 @@ int nk_jv_batched(nk_ctx* c, const nk_problem* p, int32_t k, double* const* out,
     for (int b = 0; b < k; ++b)
         if (!out[b] || !v[b]) return NK_E_ARG;
     Geo g{};
-    if (!nk_is_user(p->kind)) NK_TRY(geometry(c, p, &g));
+    if (!kind_of(p->kind).user) NK_TRY(geometry(c, p, &g));
     // a user residual has no batched kernel, and 3D blocks take their x / y ghost layers from faces the
     // batched kernel does not read: one product per column (each bit-identical to the batched form)
-    if (nk_is_user(p->kind) || blocks3d(c, g)) {
+    if (kind_of(p->kind).user || blocks3d(c, g)) {
         for (int b = 0; b < k; ++b) NK_TRY(nk_jv(c, p, out[b], u, v[b], F0, mode, eps));
         return NK_OK;
     }
@@ -503,7 +477,7 @@ int nk_jv_batched(nk_ctx* c, const nk_problem* p, int32_t k, double* const* out,
 
 int nk_jtv_batched(nk_ctx* c, const nk_problem* p, int32_t k, double* const* out, const double* u, const double* const* v) {
     if (!c || !p || !out || !u || !v || k < 0) return NK_E_ARG;
-    if (!nk_is_user(p->kind))  // symmetric Jacobians: J^T V = J V, the exact tangent
+    if (!kind_of(p->kind).user)  // symmetric Jacobians: J^T V = J V, the exact tangent
         return nk_jv_batched(c, p, k, out, u, v, nullptr, NK_JV_EXACT, 0.0);
     for (int b = 0; b < k; ++b) NK_TRY(nk_jtv(c, p, out[b], u, v[b]));
     return NK_OK;
@@ -513,7 +487,7 @@ int nk_jacobian_collect(nk_ctx* c, const nk_problem* p, const double* u, int32_t
                         int64_t* rowval, double* nzval, int64_t cap, int64_t* nnz) {
     if (!c || !p || !u || !colptr || !nnz || cap < 0 || (cap > 0 && (!rowval || !nzval))) return NK_E_ARG;
     if (c->nranks > 1) return fail(c, NK_E_ARG, "collect(J) of a distributed operator: gather the slabs first");
-    if (!nk_is_user(p->kind)) {  // symmetric pattern and values: collect(transpose(J)) == collect(J)
+    if (!kind_of(p->kind).user) {  // symmetric pattern and values: collect(transpose(J)) == collect(J)
         const int rc = collect_stencil(c, p, u, colptr, rowval, nzval, cap, nnz);
         if (rc != 1) return rc;
     }

@@ -19,64 +19,30 @@ int fail(nk_ctx* c, int code, const std::string& msg) {
 int geometry(nk_ctx* c, const nk_problem* p, Geo* g) {
     if (!p) return fail(c, NK_E_ARG, "null problem");
     if (p->nx < 1 || p->ny < 1 || p->nz < 1) return fail(c, NK_E_ARG, "grid extents must be >= 1");
-    switch (p->kind) {
-    case NK_BRATU1D:
-        if (p->ny != 1 || p->nz != 1) return fail(c, NK_E_ARG, "1D problem needs ny = nz = 1");
-        g->dim = 1; g->plane = 1; g->nplanes = p->nx;
-        break;
-    case NK_BRATU2D:
-    case NK_HEAT2D_EULER:
-    case NK_HEAT2D_MIDPOINT:
-    case NK_HEAT2D_TRAPEZOID:
-        if (p->nz != 1) return fail(c, NK_E_ARG, "2D problem needs nz = 1");
-        g->dim = 2; g->plane = p->nx; g->nplanes = p->ny;
-        break;
-    case NK_HEAT3D_EULER:
-    case NK_HEAT3D_MIDPOINT:
-    case NK_HEAT3D_TRAPEZOID:
-        g->dim = 3; g->plane = p->nx * p->ny; g->nplanes = p->nz;
-        break;
-    case NK_BRATU3D:
-        if (c && c->nranks > 1) return fail(c, NK_E_ARG, "3D Bratu runs on one rank (z-slabs and 3D blocks are not implemented for it)");
-        g->dim = 3; g->plane = p->nx * p->ny; g->nplanes = p->nz;
-        break;
-    case NK_IGNITION2D_EULER:
-    case NK_IGNITION2D_MIDPOINT:
-    case NK_IGNITION2D_TRAPEZOID:
-        if (p->nz != 1) return fail(c, NK_E_ARG, "2D problem needs nz = 1");
-        if (p->bc == NK_BC_PERIODIC) return fail(c, NK_E_ARG, "the ignition kinds have bc_zero! only (periodic boundaries are not implemented for them)");
-        if (c && c->nranks > 1) return fail(c, NK_E_ARG, "the ignition kinds run on one rank (slabs are not implemented for them)");
-        g->dim = 2; g->plane = p->nx; g->nplanes = p->ny;
-        break;
-    case NK_USER1D:
-    case NK_USER2D:
-    case NK_USER3D:
-        if (!p->user || !p->user->F) return fail(c, NK_E_ARG, "user problem needs user->F");
-        if (p->kind == NK_USER1D) {
-            if (p->ny != 1 || p->nz != 1) return fail(c, NK_E_ARG, "1D problem needs ny = nz = 1");
-            g->dim = 1; g->plane = 1; g->nplanes = p->nx;
-        } else if (p->kind == NK_USER2D) {
-            if (p->nz != 1) return fail(c, NK_E_ARG, "2D problem needs nz = 1");
-            g->dim = 2; g->plane = p->nx; g->nplanes = p->ny;
-        } else {
-            g->dim = 3; g->plane = p->nx * p->ny; g->nplanes = p->nz;
-        }
-        break;
-    default:
-        return fail(c, NK_E_ARG, "unknown problem kind");
-    }
+    const Kind K = kind_of(p->kind);
+    if (K.dim == 0) return fail(c, NK_E_ARG, "unknown problem kind");
+    if (K.user && (!p->user || !p->user->F)) return fail(c, NK_E_ARG, "user problem needs user->F");
+    if (K.dim == 1 && (p->ny != 1 || p->nz != 1)) return fail(c, NK_E_ARG, "1D problem needs ny = nz = 1");
+    if (K.dim == 2 && p->nz != 1) return fail(c, NK_E_ARG, "2D problem needs nz = 1");
+    if (K.ignition && p->bc == NK_BC_PERIODIC) return fail(c, NK_E_ARG, "the ignition kinds have bc_zero! only (periodic boundaries are not implemented for them)");
+    if (!K.ranks && c && c->nranks > 1)
+        return fail(c, NK_E_ARG, K.ignition ? "the ignition kinds run on one rank (slabs are not implemented for them)"
+                                            : "3D Bratu runs on one rank (z-slabs and 3D blocks are not implemented for it)");
+    g->dim = K.dim;
+    g->plane = K.dim == 1 ? 1 : (K.dim == 2 ? p->nx : p->nx * p->ny);
+    g->nplanes = K.dim == 1 ? p->nx : (K.dim == 2 ? p->ny : p->nz);
     if (p->bc == NK_BC_PERIODIC) {
-        if (!nk_is_heat(p->kind)) return fail(c, NK_E_ARG, "periodic boundaries are defined for the heat problems (bc_periodic!)");
+        if (!K.periodic) return fail(c, NK_E_ARG, "periodic boundaries are defined for the heat problems (bc_periodic!)");
         // every wrapped axis needs >= 3 points (the slab axis: the whole grid when not distributed)
         if (p->nx < 3 || (g->dim == 3 && p->ny < 3) || (c->nranks <= 1 && g->nplanes < 3))
             return fail(c, NK_E_ARG, "periodic boundaries need >= 3 points along every axis");
     } else if (p->bc != NK_BC_ZERO) {
         return fail(c, NK_E_ARG, "unknown boundary condition");
     }
-    if (nk_has_un(p->kind) && !p->un) return fail(c, NK_E_ARG, nk_is_heat(p->kind) ? "heat problem needs u_n" : "ignition problem needs u_n");
+    if (K.un && !p->un) return fail(c, NK_E_ARG, K.heat ? "heat problem needs u_n" : "ignition problem needs u_n");
     if (g->dim == 3 && c && c->px * c->py > 1) {  // 3D blocks (nk_dist_grid)
         if (p->bc == NK_BC_PERIODIC) return fail(c, NK_E_ARG, "3D blocks: bc_zero! only (periodic problems use z-slabs)");
-        if (nk_is_user(p->kind)) return fail(c, NK_E_ARG, "3D blocks: built-in residuals only (user residuals use z-slabs)");
+        if (!K.blocks3d) return fail(c, NK_E_ARG, "3D blocks: built-in residuals only (user residuals use z-slabs)");
     }
     g->n = p->nx * p->ny * p->nz;
     g->front = (g->plane + 31) / 32 * 32;
@@ -385,7 +351,7 @@ int nk_jacobian_diag(nk_ctx* c, const nk_problem* p, double* out, const double* 
     if (!c || !out || !u) return NK_E_ARG;
     Geo g;
     NK_TRY(geometry(c, p, &g));
-    if (nk_is_user(p->kind)) return fail(c, NK_E_ARG, "diag(J) of a user residual: probe it with collect(J)");
+    if (kind_of(p->kind).user) return fail(c, NK_E_ARG, "diag(J) of a user residual: probe it with collect(J)");
     return launch_jdiag(c, p, out, u, reciprocal);
 }
 
@@ -393,7 +359,7 @@ int nk_ilu0_factor(nk_ctx* c, const nk_problem* p, const double* u, double* dtil
     if (!c || !dtilde || !u) return NK_E_ARG;
     Geo g;
     NK_TRY(geometry(c, p, &g));
-    if (nk_is_user(p->kind)) return fail(c, NK_E_ARG, "ILU(0) of a user residual: assemble it with collect(J)");
+    if (kind_of(p->kind).user) return fail(c, NK_E_ARG, "ILU(0) of a user residual: assemble it with collect(J)");
     if (p->bc == NK_BC_PERIODIC) return fail(c, NK_E_ARG, "ILU(0) is implemented for bc_zero! (the wrap breaks the banded pattern)");
     NK_TRY(launch_jdiag(c, p, dtilde, u, 0));
     NK_TRY(launch_ilu0_factor(c, p, g.dim, dtilde));
@@ -413,7 +379,7 @@ int nk_jtv(nk_ctx* c, const nk_problem* p, double* out, const double* u, const d
     if (!c || !out || !u || !v) return NK_E_ARG;
     Geo g;
     NK_TRY(geometry(c, p, &g));
-    if (!nk_is_user(p->kind))  // symmetric Jacobians: J^T v = J v, the exact tangent
+    if (!kind_of(p->kind).user)  // symmetric Jacobians: J^T v = J v, the exact tangent
         return nk_jv(c, p, out, u, v, nullptr, NK_JV_EXACT, 0.0);
     const nk_user_ops* ops = p->user;
     if (!ops->JT) return fail(c, NK_E_ARG, "transpose product of a user problem needs user->JT");

@@ -27,19 +27,9 @@ struct MbInfo {
 hipError_t resident_bind_mb(const MbInfo& m);  // nk_resident.hip's copy of g_mb
 hipError_t kernels_bind_mb(const MbInfo& m);   // nk_kernels.hip's copy
 hipError_t minres_bind_mb(const MbInfo& m);    // nk_minres.hip's copy
-// the stencil instantiation units' copies (nk_stencil_inst.hip, one per problem kind)
-hipError_t stencil_bind_mb_1(const MbInfo& m);
-hipError_t stencil_bind_mb_2(const MbInfo& m);
-hipError_t stencil_bind_mb_3(const MbInfo& m);
-hipError_t stencil_bind_mb_4(const MbInfo& m);
-hipError_t stencil_bind_mb_5(const MbInfo& m);
-hipError_t stencil_bind_mb_6(const MbInfo& m);
-hipError_t stencil_bind_mb_7(const MbInfo& m);
-hipError_t stencil_bind_mb_8(const MbInfo& m);
-hipError_t stencil_bind_mb_9(const MbInfo& m);
-hipError_t stencil_bind_mb_20(const MbInfo& m);
-hipError_t stencil_bind_mb_21(const MbInfo& m);
-hipError_t stencil_bind_mb_22(const MbInfo& m);
+// the stencil instantiation units' copies (nk_stencil_inst.hip, one per kind of kStencilKinds)
+template <int KIND>
+hipError_t stencil_bind_mb(const MbInfo& m);
 
 typedef double dx2 __attribute__((ext_vector_type(2)));  // 16-B streaming element
 

@@ -92,7 +92,7 @@ int halo_exchange(nk_ctx* c, const nk_problem* p, const double* v) {
 }
 
 int exchange_un(nk_ctx* c, const nk_problem* p) {
-    if (!p || !nk_has_un(p->kind) || nk_scheme(p->kind) == 0 || !p->un) return NK_OK;
+    if (!p || !kind_of(p->kind).un || kind_of(p->kind).scheme == 0 || !p->un) return NK_OK;
     return halo_exchange(c, p, p->un);
 }
 

@@ -44,10 +44,12 @@ int mailbox_bind(nk_ctx* c) {
     }
     NK_HIP(c, hipMemcpyToSymbol(HIP_SYMBOL(g_mb), &m, sizeof(m)));
     // and the copy in every other unit: BLAS-1 / MGS, the stencil instantiations, the resident sweep, MINRES
-    for (auto bind : {kernels_bind_mb, stencil_bind_mb_1, stencil_bind_mb_2, stencil_bind_mb_3, stencil_bind_mb_4, stencil_bind_mb_5,
-                      stencil_bind_mb_6, stencil_bind_mb_7, stencil_bind_mb_8, stencil_bind_mb_9, stencil_bind_mb_20,
-                      stencil_bind_mb_21, stencil_bind_mb_22, resident_bind_mb, minres_bind_mb})
-        NK_HIP(c, bind(m));
+    for (auto bind : {kernels_bind_mb, resident_bind_mb, minres_bind_mb}) NK_HIP(c, bind(m));
+    for (int kind : kStencilKinds) {
+        hipError_t e = hipSuccess;
+        for_kind(kind, [&](auto K) { e = stencil_bind_mb<decltype(K)::value>(m); });
+        NK_HIP(c, e);
+    }
     return NK_OK;
 }
 

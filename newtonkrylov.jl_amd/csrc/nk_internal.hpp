@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "nkhip.h"
+#include "nk_kind.hpp"
 #include "nk_plan.hpp"
 
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -354,18 +355,6 @@ struct Range {
     Range(const Range&) = delete;
     Range& operator=(const Range&) = delete;
 };
-
-inline bool nk_is_user(int kind) { return kind >= NK_USER1D && kind <= NK_USER3D; }
-inline bool nk_is_heat(int kind) { return kind >= NK_HEAT2D_EULER && kind <= NK_HEAT3D_TRAPEZOID; }
-// the ignition kinds: an implicit scheme composed with f(u) = a Δu + λ exp(u) (2D, one rank, bc_zero!)
-inline bool nk_is_ignition(int kind) { return kind >= NK_IGNITION2D_EULER && kind <= NK_IGNITION2D_TRAPEZOID; }
-// the kinds that carry u_n (a, Δt, α with it): the implicit schemes, whatever f they are composed with
-inline bool nk_has_un(int kind) { return nk_is_heat(kind) || nk_is_ignition(kind); }
-// implicit.jl scheme of a heat or ignition kind: 0 G_Euler!, 1 G_Midpoint!, 2 G_Trapezoid!
-inline int nk_scheme(int kind) {
-    return (kind == NK_HEAT2D_MIDPOINT || kind == NK_HEAT3D_MIDPOINT || kind == NK_IGNITION2D_MIDPOINT) ? 1
-           : ((kind == NK_HEAT2D_TRAPEZOID || kind == NK_HEAT3D_TRAPEZOID || kind == NK_IGNITION2D_TRAPEZOID) ? 2 : 0);
-}
 
 // ---------------------------------------------------------------- distribution (nk_dist.cpp)
 // 3D blocks (nk_dist_grid with px * py > 1): a 3D grid function's allocation carries, after its trailing

@@ -100,14 +100,14 @@ extern "C" int nkb_stencil3d_ex(nk_ctx* c, int64_t n, int64_t nz, int kind, int 
     return NK_OK;
 }
 
-// any stencil kind (NK_BRATU2D .. NK_HEAT3D_TRAPEZOID, NK_BRATU3D, NK_IGNITION2D_*) at nx x ny x nz (nz = 1 for the 2D kinds): mode / epi, rows (2D: rows per tile;
+// any 2D / 3D stencil kind (kStencilKinds) at nx x ny x nz (nz = 1 for the 2D kinds): mode / epi, rows (2D: rows per tile;
 // 3D: planes per z-march; 0: the launcher's choice), variant bits `fast` -- microseconds per launch
 extern "C" int nkb_stencil_kind(nk_ctx* c, int kind, int64_t nx, int64_t ny, int64_t nz, int mode, int epi, int rows,
                                 int fast, int reps, double* us_out) {
     using namespace nk;
-    if (!c || nx < 3 || ny < 3 || nz < 1 || reps < 1 || !us_out || ((kind < NK_BRATU2D || kind > NK_HEAT3D_TRAPEZOID) && kind != NK_BRATU3D && !nk_is_ignition(kind)))
+    if (!c || nx < 3 || ny < 3 || nz < 1 || reps < 1 || !us_out || !stencil_kind(kind) || kind_of(kind).dim == 1)
         return NK_E_ARG;
-    if (nk_is_ignition(kind) && nz != 1) return nk::fail(c, NK_E_ARG, "the ignition kinds are 2D (nz = 1)");
+    if (kind_of(kind).ignition && nz != 1) return nk::fail(c, NK_E_ARG, "the ignition kinds are 2D (nz = 1)");
     // NK_BRATU3D has k_st3l only (4- or 8-row tiles): the y-march bit is refused here, and the NK_ST3_LDS=0 /
     // NK_ST3_YMARCH=1 knobs do not apply to it (launch_stencil_ex plans k_st3l for the kind whatever they say, and the
     // profile names the instantiation that ran)
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void k_hashfill2(int64_t n, double* __restr
 extern "C" int nkb_stencil_cmp(nk_ctx* c, int kind, int64_t nx, int64_t ny, int64_t nz, int mode, int epi, int fa, int fb,
                                double* diff) {
     using namespace nk;
-    if (!c || nx < 3 || ny < 3 || nz < 1 || !diff || ((kind < NK_BRATU2D || kind > NK_HEAT3D_TRAPEZOID) && kind != NK_BRATU3D && !nk_is_ignition(kind)))
+    if (!c || nx < 3 || ny < 3 || nz < 1 || !diff || !stencil_kind(kind) || kind_of(kind).dim == 1)
         return NK_E_ARG;
     if (kind == NK_BRATU3D && ((fa | fb) & 524288)) return nk::fail(c, NK_E_ARG, "NK_BRATU3D has no y-march (k_st3y) variant");
     const double h = 1.0 / (nx + 1);

@@ -608,10 +608,10 @@ double st_bytes(const StencilIn& in, int64_t n, const StInst& st) {
     // u_n: the implicit schemes; u in the exact tangent: the kinds with λ exp(u) (the ignition Midpoint tangent
     // exponentiates α u_n + (1 - α) u: u_n as well)
     const int kind = in.p->kind;
-    const bool un = nk_has_un(kind), heat = nk_is_heat(kind);
+    const bool un = kind_of(kind).un;
     int words = 1;  // out
     if (in.mode == MODE_RES) words += 1 + (un ? 1 : 0);
-    else if (in.mode == MODE_JEXACT) words += 1 + (heat ? 0 : 1) + (kind == NK_IGNITION2D_MIDPOINT ? 1 : 0);
+    else if (in.mode == MODE_JEXACT) words += 1 + (kind_of(kind).exp ? 1 : 0) + (jexact_reads_un(kind) ? 1 : 0);
     else words += 3 + (un ? 1 : 0) - (st.f0r ? 1 : 0);
     if (in.epi == EPI_RESID || (in.epi == EPI_DOT && in.aux)) words += 1;
     if (in.vout) words += 1;  // fused kdivcopy!: V_k is written
@@ -628,7 +628,7 @@ const char* const kStV1Names[3] = {"residual", "jv_exact_dot_v1", "jv_fd_dot_v1"
 }  // namespace
 
 int launch_stencil(nk_ctx* c, const StencilIn& in, Red* red) {
-    if (in.p && nk_is_user(in.p->kind)) {
+    if (in.p && kind_of(in.p->kind).user) {
         if (in.xchg_v) NK_TRY(halo_exchange(c, in.p, in.v));
         return launch_user(c, in, red);
     }
@@ -647,13 +647,13 @@ int launch_stencil_ex(nk_ctx* c, const StencilIn& in, Red* red, int rows_overrid
         knobs.ymarch = 0;
         fast &= ~524288;
     }
-    if (nk_is_ignition(p->kind)) {  // the VEC 1 / 2 row march is the kinds' only kernel (no VEC 4, no one-shot tiles)
+    if (kind_of(p->kind).ignition) {  // the VEC 1 / 2 row march is the kinds' only kernel (no VEC 4, no one-shot tiles)
         knobs.vec_pref = 2;
         knobs.oneshot = 0;
         fast &= ~(4 | 8192 | 16384 | 32768 | 131072);
     }
-    const StPlan P = st_plan(StShape{g.dim, p->nx, p->ny, p->nz, per, blk, in.mode, nk_is_heat(p->kind), nk_scheme(p->kind),
-                                     vstore, in.aux != nullptr, rows_override, fast, in.f0r && st_kind_f0r(p->kind)},
+    const StPlan P = st_plan(StShape{g.dim, p->nx, p->ny, p->nz, per, blk, in.mode, kind_of(p->kind).heat, kind_of(p->kind).scheme,
+                                     vstore, in.aux != nullptr, rows_override, fast, in.f0r && kind_of(p->kind).f0r},
                              knobs);
     KArgs A{};
     A.out = in.out; A.u = in.u; A.v = in.v; A.F0 = in.F0; A.un = p->un; A.aux = in.aux;
@@ -722,28 +722,20 @@ int launch_stencil_ex(nk_ctx* c, const StencilIn& in, Red* red, int rows_overrid
     const char* kname = epi == EPI_DOTV ? kStFusedNames[mode] : (epi == EPI_DOTVS ? kStV1Names[mode] : kStNames[mode][epi]);
     StInst st{};
     const char* stname = st.name;
+    bool known = true;
     const int rc = launch_dyn(c, kname, [&] {
-        switch (kind) {  // one translation unit per kind (nk_stencil_inst.hip)
-        case NK_BRATU1D: st = stencil_kind_1(A, mode, epi, vec, grid, s, false); break;
-        case NK_BRATU2D: st = stencil_kind_2(A, mode, epi, vec, grid, s, false); break;
-        case NK_HEAT2D_EULER: st = stencil_kind_3(A, mode, epi, vec, grid, s, per); break;
-        case NK_HEAT3D_EULER: st = stencil_kind_4(A, mode, epi, vec, grid, s, per); break;
-        case NK_HEAT2D_MIDPOINT: st = stencil_kind_5(A, mode, epi, vec, grid, s, per); break;
-        case NK_HEAT3D_MIDPOINT: st = stencil_kind_6(A, mode, epi, vec, grid, s, per); break;
-        case NK_HEAT2D_TRAPEZOID: st = stencil_kind_7(A, mode, epi, vec, grid, s, per); break;
-        case NK_HEAT3D_TRAPEZOID: st = stencil_kind_8(A, mode, epi, vec, grid, s, per); break;
-        case NK_BRATU3D: st = stencil_kind_9(A, mode, epi, vec, grid, s, false); break;
-        case NK_IGNITION2D_EULER: st = stencil_kind_20(A, mode, epi, vec, grid, s, false); break;
-        case NK_IGNITION2D_MIDPOINT: st = stencil_kind_21(A, mode, epi, vec, grid, s, false); break;
-        case NK_IGNITION2D_TRAPEZOID: st = stencil_kind_22(A, mode, epi, vec, grid, s, false); break;
-        default: break;  // (geometry has refused every other kind)
-        }
+        known = for_kind(kind, [&](auto K) {  // one translation unit per kind (nk_stencil_inst.hip)
+            constexpr int KIND = decltype(K)::value;
+            st = stencil_launch<KIND>(A, mode, epi, vec, grid, s, per && kind_of(KIND).periodic);
+        });
+        if (!known) return 0.0;
         if (A.group > 1) {  // one-shot tiles: the group sums in tile order, as the next kernel's partials
             const int ng = (grid + A.group - 1) / A.group;
             hipLaunchKernelGGL(k_tile_fold, dim3(ng), dim3(64), 0, s, A.tpart, A.group, grid, A.part, A.fin);
         }
         return st_bytes(in, g.n, st);
     }, -1.0, &stname);
+    if (!known) return fail(c, NK_E_ARG, "stencil launch: not a built-in stencil kind");
     if (rc == NK_OK && mode == MODE_JFD) ++(st.f0r ? c->n_fd_f0r : c->n_fd_f0_read);
     return rc;
 }

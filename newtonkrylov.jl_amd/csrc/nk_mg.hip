@@ -581,8 +581,6 @@ int mg_free(nk_mg* m) {
     return NK_OK;
 }
 
-bool mg_kind_ok(int kind) { return (kind >= NK_BRATU1D && kind <= NK_HEAT3D_TRAPEZOID) || kind == NK_BRATU3D || nk_is_ignition(kind); }
-
 // slabs: pos[l] / neg[l] of this rank's rows -> of the whole level, through the context's cross-rank sum.  Every rank
 // adds 1 (positive) + 64 (negative) per level (at most kMbRanks = 32 < 64 ranks: no carry), four levels of 12 bits to
 // a scalar (exact in a double); a level is positive / negative when the count is nranks.  One host sync per scalar.
@@ -727,7 +725,7 @@ namespace {
 // the hierarchy on the level extents `given` (nlevels of them; validated here), or on mg_plan's when null
 int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int64_t* given, int32_t nlevels, nk_mg** out) {
     if (!c || !p || !out) return NK_E_ARG;
-    if (nk_is_user(p->kind) || !mg_kind_ok(p->kind))
+    if (!stencil_kind(p->kind))
         return fail(c, NK_E_ARG, "multigrid: built-in stencil kinds only (a user residual's coefficients are unknown; "
                                  "give them with nk_mg_set_operator on a built-in kind's grid)");
     if (p->bc != NK_BC_ZERO) return fail(c, NK_E_ARG, "multigrid: bc_zero! only (periodic boundaries are not implemented)");
@@ -737,11 +735,11 @@ int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int6
     const bool dist = c->nranks != 1;
     if (dist && (c->px * c->py > 1 || block_self(c)))
         return fail(c, NK_E_ARG, "multigrid: slabs only on a distributed context (3D blocks are not implemented)");
-    if (dist && p->kind == NK_BRATU1D) return fail(c, NK_E_ARG, "multigrid: 1D kinds are not implemented on a distributed context");
-    if (dist && p->kind == NK_BRATU3D)
-        return fail(c, NK_E_ARG, "multigrid: NK_BRATU3D runs on one rank (a distributed context is not implemented for it)");
-    if (dist && nk_is_ignition(p->kind))
-        return fail(c, NK_E_ARG, "multigrid: the ignition kinds run on one rank (a distributed context is not implemented for them)");
+    const Kind K = kind_of(p->kind);
+    if (dist && K.dim == 1) return fail(c, NK_E_ARG, "multigrid: 1D kinds are not implemented on a distributed context");
+    if (dist && !K.ranks)
+        return fail(c, NK_E_ARG, K.ignition ? "multigrid: the ignition kinds run on one rank (a distributed context is not implemented for them)"
+                                            : "multigrid: NK_BRATU3D runs on one rank (a distributed context is not implemented for it)");
     if (dist && given)
         return fail(c, NK_E_ARG, "multigrid: a level list (semicoarsening) is not implemented on a distributed context");
     Geo g;
@@ -903,11 +901,11 @@ int nk_mg_set_jacobian(nk_mg* m, const nk_problem* p, const double* u) {
         return fail(c, NK_E_ARG, "multigrid: the problem does not match the hierarchy's (kind, grid, spacings, bc_zero!)");
     double k[3] = {0.0, 0.0, 0.0};
     const int64_t n = m->lv[0].n;
-    if (nk_is_ignition(p->kind)) {
+    if (kind_of(p->kind).ignition) {
         // J = θ Δt (a L + λ diag(exp(m))) - I: k_a = θ a Δt as for the heat kinds, s = θ Δt λ exp(m) - 1 with m = u
         // (G_Midpoint!: α u_n + (1 - α) u).  s turns positive where θ Δt λ exp(m) > 1 (near blow-up): the diagonal then
         // changes sign on some level and mg_setup truncates the hierarchy there, as for Bratu above the fold
-        const int sch = nk_scheme(p->kind);
+        const int sch = kind_of(p->kind).scheme;
         const double theta = sch == 1 ? 1.0 - p->alpha : (sch == 2 ? 0.5 : 1.0);
         if (!p->un) return fail(c, NK_E_ARG, "ignition problem needs u_n");
         for (int a = 0; a < m->dim; ++a) k[a] = theta * p->a * p->dt;
@@ -923,8 +921,8 @@ int nk_mg_set_jacobian(nk_mg* m, const nk_problem* p, const double* u) {
         NK_TRY(launch(c, "mg_setup_s", 16.0 * n, [&] {
             hipLaunchKernelGGL(k_mg_ign_s, dim3(wide_blocks(n)), dim3(kBlock), 0, c->stream, (int)n, coef, m->s[0]);
         }));
-    } else if (nk_is_heat(p->kind)) {
-        const int sch = nk_scheme(p->kind);
+    } else if (kind_of(p->kind).heat) {
+        const int sch = kind_of(p->kind).scheme;
         const double theta = sch == 1 ? 1.0 - p->alpha : (sch == 2 ? 0.5 : 1.0);
         for (int a = 0; a < m->dim; ++a) k[a] = theta * p->a * p->dt;
         NK_TRY(launch_fill(c, n, m->s[0], -1.0));

@@ -30,10 +30,6 @@ constexpr int kResTail = NK_RES_TAIL_DEFAULT;
 
 enum Mode { MODE_RES = 0, MODE_JEXACT = 1, MODE_JFD = 2 };
 
-// the kind has F0R instantiations (k_st2d / k_st3l<..., F0R>: F0 recomputed from u): every built-in kind but the
-// ignition kinds (20 .. 22, include/nkhip.h), whose FD launches always read F0 -- the launcher clears StShape::f0r
-constexpr bool st_kind_f0r(int kind) { return kind < 20 || kind > 22; }
-
 // ---------------------------------------------------------------- streaming grids
 // grid size of streaming reductions: >= 4 double2 per thread, at most `cap` (kMaxRedBlocks) blocks
 inline int red_blocks(int64_t n, int cap) {

@@ -53,12 +53,12 @@ __global__ __launch_bounds__(kBlock) void k_jdiag(KArgs A, double* __restrict__ 
     const int64_t n = A.nx * A.ny * A.nz;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
         // G_Midpoint!'s stencil field is (1 - α) v: its centre (1 - α), the "- v" term 1
-        const double c = scheme_of<KIND>() == 1 ? (1.0 - A.alpha) * 1.0 : 1.0;
+        const double c = kind_of(KIND).scheme == 1 ? (1.0 - A.alpha) * 1.0 : 1.0;
         double lsum = lapk(A, c, 0.0, 0.0, A.hx2, A.ihx2);
         if (DIM >= 2) lsum = lsum + lapk(A, c, 0.0, 0.0, A.hy2, A.ihy2);
         if (DIM == 3) lsum = lsum + lapk(A, c, 0.0, 0.0, A.hz2, A.ihz2);
-        const double uc = kind_has_exp(KIND) ? A.u[i] : 0.0;
-        const double unc = KIND == NK_IGNITION2D_MIDPOINT ? A.un[i] : 0.0;  // its tangent exponentiates α u_n + (1 - α) u
+        const double uc = kind_of(KIND).exp ? A.u[i] : 0.0;
+        const double unc = jexact_reads_un(KIND) ? A.un[i] : 0.0;  // its tangent exponentiates α u_n + (1 - α) u
         bool rare_ = false;
         const double d = point_value<KIND, MODE_JEXACT>(A, c, lsum, uc, unc, 0.0, 1.0, 0.0, &NKX_T[0][0], rare_);
         out[i] = recip ? 1.0 / d : d;
@@ -94,25 +94,14 @@ int launch_jdiag(nk_ctx* c, const nk_problem* p, double* out, const double* u, i
     A.lam = p->lambda; A.a = p->a; A.dt = p->dt; A.alpha = p->alpha;
     const int64_t n = p->nx * p->ny * p->nz;
     const int g = (int)std::min<int64_t>((n + kBlock - 1) / kBlock, 4096);
-#define NK_JDIAG(K, D) hipLaunchKernelGGL((k_jdiag<K, D>), dim3(g), dim3(kBlock), 0, c->stream, A, out, recip)
-    return launch(c, "jacobian_diag", 16.0 * n, [&] {
-        switch (p->kind) {
-        case NK_BRATU1D: NK_JDIAG(NK_BRATU1D, 1); break;
-        case NK_BRATU2D: NK_JDIAG(NK_BRATU2D, 2); break;
-        case NK_HEAT2D_EULER: NK_JDIAG(NK_HEAT2D_EULER, 2); break;
-        case NK_HEAT2D_MIDPOINT: NK_JDIAG(NK_HEAT2D_MIDPOINT, 2); break;
-        case NK_HEAT2D_TRAPEZOID: NK_JDIAG(NK_HEAT2D_TRAPEZOID, 2); break;
-        case NK_HEAT3D_MIDPOINT: NK_JDIAG(NK_HEAT3D_MIDPOINT, 3); break;
-        case NK_HEAT3D_TRAPEZOID: NK_JDIAG(NK_HEAT3D_TRAPEZOID, 3); break;
-        case NK_HEAT3D_EULER: NK_JDIAG(NK_HEAT3D_EULER, 3); break;
-        case NK_BRATU3D: NK_JDIAG(NK_BRATU3D, 3); break;
-        case NK_IGNITION2D_EULER: NK_JDIAG(NK_IGNITION2D_EULER, 2); break;
-        case NK_IGNITION2D_MIDPOINT: NK_JDIAG(NK_IGNITION2D_MIDPOINT, 2); break;
-        case NK_IGNITION2D_TRAPEZOID: NK_JDIAG(NK_IGNITION2D_TRAPEZOID, 2); break;
-        default: break;  // (geometry has refused every other kind)
-        }
+    bool known = true;
+    const int rc = launch(c, "jacobian_diag", 16.0 * n, [&] {
+        known = for_kind(p->kind, [&](auto K) {
+            constexpr int KIND = decltype(K)::value;
+            hipLaunchKernelGGL((k_jdiag<KIND, kind_of(KIND).dim>), dim3(g), dim3(kBlock), 0, c->stream, A, out, recip);
+        });
     });
-#undef NK_JDIAG
+    return known ? rc : fail(c, NK_E_ARG, "diag(J): not a built-in stencil kind");
 }
 
 // ------------------------------------------------------------------------------ ILU(0)
@@ -342,10 +331,10 @@ __global__ __launch_bounds__(64) void k_ilu0_pipe(IluPipe P) {
 // other axes add +0, Bratu adds λ (e^u · 0) = +0, heat: (Δt or Δt/2) (a lap) - 0; the ignition kinds: the heat kind's
 // value, since a lap + λ (e^m · 0) = a lap + 0
 double ilu_offdiag(const nk_problem* p, double h) {
-    const int sch = nk_has_un(p->kind) ? nk_scheme(p->kind) : 0;
+    const int sch = kind_of(p->kind).scheme;
     const double f = sch == 1 ? (1.0 - p->alpha) * 1.0 : 1.0;
     const double lsum = ((f - 2.0 * 0.0) + 0.0) / (h * h);
-    if (!nk_has_un(p->kind)) return lsum;
+    if (!kind_of(p->kind).un) return lsum;
     return (sch == 2 ? p->dt / 2.0 : p->dt) * (p->a * lsum) - 0.0;
 }
 

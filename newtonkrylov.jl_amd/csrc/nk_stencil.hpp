@@ -3,7 +3,7 @@
 // x-edges, the XCD-aware tile orders.  The 2D / 3D kernel templates and their dispatch are in
 // nk_stencil_kern.hpp; each kind is instantiated in its own translation unit (nk_stencil_inst.hip,
 // compiled once per NK_ST_KIND) so the build parallelises; nk_kernels.hip reaches them through the
-// stencil_kind_<K> entry points.
+// stencil_launch<KIND> entry points.
 #pragma once
 #include <cstdio>
 #include <type_traits>
@@ -66,38 +66,12 @@ struct StInst {
     bool f0r;
 };
 
-// per-kind entry points (nk_stencil_inst.hip): launch one stencil kernel of kind K / bind its g_mb
-#define NK_ST_DECL(K)                                                                                      \
-    StInst stencil_kind_##K(const KArgs& A, int mode, int epi, int vec, int grid, hipStream_t s, bool per); \
-    hipError_t stencil_bind_mb_##K(const MbInfo& m);
-NK_ST_DECL(1)
-NK_ST_DECL(2)
-NK_ST_DECL(3)
-NK_ST_DECL(4)
-NK_ST_DECL(5)
-NK_ST_DECL(6)
-NK_ST_DECL(7)
-NK_ST_DECL(8)
-NK_ST_DECL(9)
-NK_ST_DECL(20)
-NK_ST_DECL(21)
-NK_ST_DECL(22)
-#undef NK_ST_DECL
+// per-kind entry point (defined and explicitly instantiated in nk_stencil_inst.hip, one object per kind):
+// launch one stencil kernel of KIND.  (stencil_bind_mb<KIND>, the object's g_mb binding: nk_device.hpp)
+template <int KIND>
+StInst stencil_launch(const KArgs& A, int mode, int epi, int vec, int grid, hipStream_t s, bool per);
 
 namespace {
-
-// implicit.jl scheme of a heat or ignition kind: 0 G_Euler! (and the Bratu kinds, NK_BRATU3D included), 1 G_Midpoint!,
-// 2 G_Trapezoid!
-template <int KIND>
-constexpr int scheme_of() {
-    return (KIND == NK_HEAT2D_MIDPOINT || KIND == NK_HEAT3D_MIDPOINT || KIND == NK_IGNITION2D_MIDPOINT)
-               ? 1
-               : ((KIND == NK_HEAT2D_TRAPEZOID || KIND == NK_HEAT3D_TRAPEZOID || KIND == NK_IGNITION2D_TRAPEZOID) ? 2 : 0);
-}
-template <int KIND>
-constexpr bool heat_kind() {  // (NK_BRATU3D = 9 lies beyond the heat range)
-    return KIND >= NK_HEAT2D_EULER && KIND <= NK_HEAT3D_TRAPEZOID;
-}
 
 // div_rn is used in the Bratu stencil objects only (nk_stencil_inst.hip with NK_ST_KIND 1 / 2: their FD Jv
 // 130 -> 126 us, profiles/r04/ab_div_rn.log); elsewhere its guard's compares and exec-mask branches cost
@@ -199,13 +173,6 @@ __device__ __forceinline__ void storevec(double* __restrict__ p, int64_t o, cons
     }
 }
 
-constexpr bool kind_bratu(int k) { return k == NK_BRATU1D || k == NK_BRATU2D || k == NK_BRATU3D; }
-// the ignition kinds: an implicit scheme composed with f(u) = a Δu + λ exp(u) -- 2D, one rank, bc_zero!
-constexpr bool kind_ignition(int k) { return k >= NK_IGNITION2D_EULER && k <= NK_IGNITION2D_TRAPEZOID; }
-// every point evaluates exp: the table in LDS (NK_EXP_LDS) and the per-lane exact phase (XM = 2)
-constexpr bool kind_has_exp(int k) { return kind_bratu(k) || kind_ignition(k); }
-// the kind carries u_n (an implicit scheme, whatever f it is composed with)
-constexpr bool kind_has_un(int k) { return (k >= NK_HEAT2D_EULER && k <= NK_HEAT3D_TRAPEZOID) || kind_ignition(k); }
 // A/B only (-DNK_ST_KEEP_VDIV): keep the runtime v / h test in every instantiation (round 3's form, where
 // the instances without the fused normalisation evaluated the division and discarded it)
 #ifdef NK_ST_KEEP_VDIV
@@ -239,8 +206,8 @@ constexpr bool kKeepVdiv = false;
 #define NK_ST2D_IGN_WPE 3
 #endif
 constexpr int st2d_wpe(int kind, int mode, bool f0r) {
-    return kind_ignition(kind) ? NK_ST2D_IGN_WPE
-           : kind_bratu(kind) ? NK_ST2D_BRATU_WPE
+    return kind_of(kind).ignition ? NK_ST2D_IGN_WPE
+           : kind_of(kind).bratu ? NK_ST2D_BRATU_WPE
                             : ((NK_ST2D_HEAT_CAP && kind == NK_HEAT2D_TRAPEZOID)
                                    ? (mode == MODE_RES ? 6 : (f0r ? 4 : 1))
                                    : 1);
@@ -250,9 +217,9 @@ constexpr int st2d_wpe(int kind, int mode, bool f0r) {
 // kinds, where every point evaluates exp: read with ds_read, its lookups never wait behind the rows the
 // march keeps in flight (a global-memory table would share their in-order vmcnt).  Declares `et`.
 #define NK_EXP_LDS(KIND)                                                                              \
-    __shared__ double et_lds[kind_has_exp(KIND) ? 256 : 2];                                           \
+    __shared__ double et_lds[kind_of(KIND).exp ? 256 : 2];                                            \
     const double* const et = et_lds;                                                                  \
-    if constexpr (kind_has_exp(KIND)) {                                                               \
+    if constexpr (kind_of(KIND).exp) {                                                                \
         for (int i_ = threadIdx.x; i_ < 256; i_ += blockDim.x) et_lds[i_] = (&NKX_T[0][0])[i_];        \
         __syncthreads();                                                                              \
     }
@@ -297,7 +264,7 @@ __device__ __forceinline__ double point_value(const KArgs& A, double c, double l
         }
     };
     (void)ex;
-    if constexpr (kind_bratu(KIND)) {
+    if constexpr (kind_of(KIND).bratu) {
 #ifdef NK_KBENCH
         if (A.fast & (1 << 20)) {  // kbench A/B only: the platform (ocml) exp, <= 1 ulp off the correctly rounded one
             if (MODE == MODE_JEXACT) return lsum + A.lam * (exp(uc) * c);
@@ -308,13 +275,13 @@ __device__ __forceinline__ double point_value(const KArgs& A, double c, double l
         if (MODE == MODE_JEXACT) return lsum + A.lam * (ex(uc) * c);  // Enzyme tangent of λ exp(u)
         const double r = lsum + A.lam * ex(c);
         return MODE == MODE_JFD ? fdq(A, r, f0c) : r;
-    } else if constexpr (kind_ignition(KIND)) {
+    } else if constexpr (kind_of(KIND).ignition) {
         // G ∘ f with f(w) = a L(w) + λ exp(w) (diffusion!'s a * (...) plus Bratu's λ * exp(u)), nothing contracted:
         //   Euler      (u_n + Δt f(w)) - w                       tangent  Δt (a L(v) + λ (exp(u) v)) - v
         //   Midpoint   (u_n + Δt f(m)) - w, m = α u_n + (1-α) w  tangent  Δt (a L(c) + λ (exp(m) c)) - v, c = (1-α) v
         //   Trapezoid  (u_n + (Δt/2) (f(u_n) + f(w))) - w        tangent  (Δt/2) (a L(v) + λ (exp(u) v)) - v
         // c = the stencil field's centre (m for Midpoint), uc / unc = the centres of u / u_n, xc the "- w" term
-        constexpr int SCH = scheme_of<KIND>();
+        constexpr int SCH = kind_of(KIND).scheme;
         if (MODE == MODE_JEXACT) {
             const double m = SCH == 1 ? A.alpha * unc + (1.0 - A.alpha) * uc : uc;
             return (SCH == 2 ? A.dt / 2.0 : A.dt) * (A.a * lsum + A.lam * (ex(m) * c)) - xc;
@@ -324,7 +291,7 @@ __device__ __forceinline__ double point_value(const KArgs& A, double c, double l
                                   : (unc + A.dt * fw) - xc;
         return MODE == MODE_JFD ? fdq(A, r, f0c) : r;
     } else {  // implicit.jl:8-37
-        constexpr int SCH = scheme_of<KIND>();
+        constexpr int SCH = kind_of(KIND).scheme;
         if (MODE == MODE_JEXACT) return (SCH == 2 ? A.dt / 2.0 : A.dt) * (A.a * lsum) - xc;
         const double r = SCH == 2 ? (unc + (A.dt / 2.0) * (A.a * lsumg + A.a * lsum)) - xc
                                   : (unc + A.dt * (A.a * lsum)) - xc;

@@ -5,17 +5,22 @@
 #ifndef NK_ST_KIND
 #error "compile with -DNK_ST_KIND=<problem kind>"
 #endif
-#define NK_CAT2(a, b) a##b
-#define NK_CAT(a, b) NK_CAT2(a, b)
 
 namespace nk {
 
-StInst NK_CAT(stencil_kind_, NK_ST_KIND)(const KArgs& A, int mode, int epi, int vec, int grid, hipStream_t s, bool per) {
-    return go_stencil_mode<NK_ST_KIND>(A, mode, epi, vec, grid, s, per);
+static_assert(stencil_kind(NK_ST_KIND), "NK_ST_KIND is not in kStencilKinds (nk_kind.hpp)");
+
+template <int KIND>
+StInst stencil_launch(const KArgs& A, int mode, int epi, int vec, int grid, hipStream_t s, bool per) {
+    return go_stencil_mode<KIND>(A, mode, epi, vec, grid, s, per);
 }
 
-hipError_t NK_CAT(stencil_bind_mb_, NK_ST_KIND)(const MbInfo& m) {
+template <int KIND>
+hipError_t stencil_bind_mb(const MbInfo& m) {
     return hipMemcpyToSymbol(HIP_SYMBOL(g_mb), &m, sizeof(m));
 }
+
+template StInst stencil_launch<NK_ST_KIND>(const KArgs&, int, int, int, int, hipStream_t, bool);
+template hipError_t stencil_bind_mb<NK_ST_KIND>(const MbInfo&);
 
 }  // namespace nk

@@ -25,7 +25,7 @@ void k_st2d(KArgs A0) {
     if constexpr (!kKeepVdiv && EPI != EPI_DOTV && EPI != EPI_DOTVS) A.vdiv = nullptr;  // v / h only with V_k stored
     A.hd = A.vdiv ? *A.vdiv : 1.0;
     A.ihd = 1.0 / A.hd;
-    constexpr int SCH = scheme_of<KIND>();
+    constexpr int SCH = kind_of(KIND).scheme;
     constexpr bool kG = SCH != 0 && MODE != MODE_JEXACT;  // u_n rows with the stencil field
     const int lane = threadIdx.x & 63;
     const int nb = gridDim.x, b = blockIdx.x;
@@ -56,9 +56,8 @@ void k_st2d(KArgs A0) {
     }
     // centre-only operands: u for the tangent of λ exp(u) (the ignition Midpoint tangent exponentiates
     // m = α u_n + (1-α) u: the centre of u_n as well); u_n where the scheme carries no u_n rows (kG)
-    constexpr bool kU = MODE == MODE_JEXACT && (KIND == NK_BRATU2D || kind_ignition(KIND));
-    constexpr bool kUn = ((KIND == NK_HEAT2D_EULER || KIND == NK_IGNITION2D_EULER) && MODE != MODE_JEXACT) ||
-                         (KIND == NK_IGNITION2D_MIDPOINT && MODE == MODE_JEXACT);
+    constexpr bool kU = MODE == MODE_JEXACT && kind_of(KIND).exp;
+    constexpr bool kUn = (kind_of(KIND).un && SCH == 0 && MODE != MODE_JEXACT) || (jexact_reads_un(KIND) && MODE == MODE_JEXACT);
     constexpr bool kF0 = MODE == MODE_JFD && !F0R;
     constexpr bool kR = MODE == MODE_JFD && F0R;  // the u field, cooked as the residual kernel cooks it
     constexpr bool kAx = EPI == EPI_DOT || EPI == EPI_DOTV || EPI == EPI_RESID;
@@ -179,7 +178,7 @@ void k_st2d(KArgs A0) {
     }
     return rare;
     };
-    if constexpr (kind_has_exp(KIND)) {
+    if constexpr (kind_of(KIND).exp) {
 #if NK_ST2D_BRATU_XM == 2
         (void)march(std::integral_constant<int, 2>{});
 #else
@@ -357,20 +356,20 @@ template <int KIND, int MODE, int EPI, int VEC, bool PER = false, int NW = 8, bo
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NK_ST3L_WPE(KIND, EPI, F0R, BLK)))) void k_st3l(KArgs A0) {
     __shared__ double sh[kShN];
     const double* et = nullptr;  // heat kinds: no exp
-    if constexpr (kind_bratu(KIND)) {  // NK_BRATU3D: the exp table in LDS, as NK_EXP_LDS copies it for the 1D / 2D kinds
+    if constexpr (kind_of(KIND).bratu) {  // NK_BRATU3D: the exp table in LDS, as NK_EXP_LDS copies it for the 1D / 2D kinds
         __shared__ double et_lds[256];
         for (int i_ = threadIdx.x; i_ < 256; i_ += blockDim.x) et_lds[i_] = (&NKX_T[0][0])[i_];
         __syncthreads();
         et = et_lds;
     }
     // the exp per lane in one pass, as the 2D Bratu march: the fast phase, the exact phase in the rare lanes
-    constexpr int XM = kind_bratu(KIND) ? 2 : 0;
+    constexpr int XM = kind_of(KIND).bratu ? 2 : 0;
     bool rare_ = false;
     KArgs A = A0;
     if constexpr (!kKeepVdiv && EPI != EPI_DOTV && EPI != EPI_DOTVS) A.vdiv = nullptr;  // v / h only with V_k stored
     A.hd = A.vdiv ? *A.vdiv : 1.0;
     A.ihd = 1.0 / A.hd;
-    constexpr int SCH = scheme_of<KIND>();
+    constexpr int SCH = kind_of(KIND).scheme;
     constexpr bool kG = SCH != 0 && MODE != MODE_JEXACT;
     constexpr bool kTG = SCH == 2 && kG;  // G_Trapezoid!: u_n's y-neighbours too
     constexpr bool kR = MODE == MODE_JFD && F0R;
@@ -442,8 +441,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NK_ST3L
 #endif
     const int64_t st = dn ? -pl : pl, dz = dn ? -1 : 1;
     const int64_t zs = dn ? z1 - 1 : z0;
-    constexpr bool kUn = SCH == 0 && MODE != MODE_JEXACT && !kind_bratu(KIND);  // G_Euler!'s u_n (Bratu has none)
-    constexpr bool kU = MODE == MODE_JEXACT && kind_bratu(KIND);  // the centre of u for the tangent of λ exp(u)
+    constexpr bool kUn = SCH == 0 && MODE != MODE_JEXACT && !kind_of(KIND).bratu;  // G_Euler!'s u_n (Bratu has none)
+    constexpr bool kU = MODE == MODE_JEXACT && kind_of(KIND).bratu;  // the centre of u for the tangent of λ exp(u)
     constexpr bool kF0 = MODE == MODE_JFD && !kR;
     constexpr bool kAx = EPI == EPI_DOT || EPI == EPI_DOTV || EPI == EPI_RESID;
     constexpr bool vout = MODE != MODE_RES && (EPI == EPI_DOTV || EPI == EPI_DOTVS);
@@ -675,11 +674,13 @@ StInst go_st3l_i(const KArgs& A, int grid, hipStream_t s) {
 template <int KIND, int MODE, int EPI, int NW>
 StInst go_st3l(const KArgs& A, int vec, int grid, hipStream_t s, bool per) {
 #ifdef NK_KBENCH
-    constexpr bool kF0R = MODE == MODE_JFD && heat_kind<KIND>();
+    constexpr bool kF0R = MODE == MODE_JFD && kind_of(KIND).heat;
 #else
-    constexpr bool kF0R = MODE == MODE_JFD && KIND == NK_HEAT3D_EULER;  // the only 3D F0R kind the launcher picks
+    // heat with G_Euler!: the only 3D F0R kind the launcher picks
+    constexpr bool kF0R = MODE == MODE_JFD && kind_of(KIND).heat && kind_of(KIND).scheme == 0;
 #endif
-    if constexpr (kind_bratu(KIND)) {  // NK_BRATU3D: one rank, bc_zero! (geometry refuses the rest): no PER / BLK instance
+    // NK_BRATU3D: one rank, bc_zero! (geometry refuses the rest): no PER / BLK instance
+    if constexpr (!kind_of(KIND).periodic && !kind_of(KIND).blocks3d) {
         return vec == 2 ? go_st3l_i<KIND, MODE, EPI, 2, false, NW, false>(A, grid, s)
                         : go_st3l_i<KIND, MODE, EPI, 1, false, NW, false>(A, grid, s);
     } else {
@@ -718,22 +719,20 @@ namespace {
 
 template <int KIND, int MODE, int EPI>
 StInst go_stencil(const KArgs& A, int vec, int grid, hipStream_t s, bool per) {
-    constexpr bool k2d = KIND == NK_BRATU2D || KIND == NK_HEAT2D_EULER || KIND == NK_HEAT2D_MIDPOINT ||
-                         KIND == NK_HEAT2D_TRAPEZOID || kind_ignition(KIND);
-    if constexpr (KIND == NK_BRATU1D) {
+    if constexpr (kind_of(KIND).dim == 1) {
         return go_st1d<MODE, EPI>(A, grid, s);
-    } else if constexpr (k2d) {
+    } else if constexpr (kind_of(KIND).dim == 2) {
 #ifdef NK_KBENCH
         // one-shot LDS tiles (k_st2t, kernel-variant build only: NK_ST_ONESHOT / fast bits)
-        if constexpr (!kind_ignition(KIND)) {  // (the ignition kinds: the row march only)
+        if constexpr (!kind_of(KIND).ignition) {  // (the ignition kinds: the row march only)
             if (A.tile2) return go_st2t<KIND, MODE, EPI>(A, vec, grid, s, per);
         }
 #endif
-        // the ignition kinds have the plain row march only: no F0R, no periodic instance (st_plan never plans F0R
-        // for them, geometry refuses bc_periodic!)
-        if constexpr (MODE == MODE_JFD && !kind_ignition(KIND)) {  // F0 recomputed from u (KArgs::f0r), VEC <= 2
+        // the ignition kinds have the plain row march only: no F0R, no periodic instance (the launcher clears the
+        // F0R request for them, geometry refuses bc_periodic!)
+        if constexpr (MODE == MODE_JFD && kind_of(KIND).f0r) {  // F0 recomputed from u (KArgs::f0r), VEC <= 2
             if (A.f0r && vec <= 2) {
-                if constexpr (heat_kind<KIND>()) {  // bc_periodic! (heat only) with F(u) recomputed
+                if constexpr (kind_of(KIND).periodic) {  // bc_periodic! (heat only) with F(u) recomputed
                     if (per) return vec == 2 ? go_st2d<KIND, MODE, EPI, 2, true, true>(A, grid, s)
                                              : go_st2d<KIND, MODE, EPI, 1, true, true>(A, grid, s);
                 }
@@ -741,12 +740,12 @@ StInst go_stencil(const KArgs& A, int vec, int grid, hipStream_t s, bool per) {
                                 : go_st2d<KIND, MODE, EPI, 1, false, true>(A, grid, s);
             }
         }
-        if constexpr (heat_kind<KIND>()) {  // bc_periodic! instantiations: heat only, VEC <= 2
+        if constexpr (kind_of(KIND).periodic) {  // bc_periodic! instantiations: heat only, VEC <= 2
             if (per) return vec == 2 ? go_st2d<KIND, MODE, EPI, 2, true>(A, grid, s)
                                      : go_st2d<KIND, MODE, EPI, 1, true>(A, grid, s);
         }
 #ifdef NK_KBENCH
-        if constexpr (!kind_ignition(KIND)) {
+        if constexpr (!kind_of(KIND).ignition) {
             if (vec == 4) return go_st2d<KIND, MODE, EPI, 4>(A, grid, s);
         }
 #endif
@@ -755,7 +754,7 @@ StInst go_stencil(const KArgs& A, int vec, int grid, hipStream_t s, bool per) {
         // k_st3l: y-neighbours through LDS, 4-row tiles (the kernel-variant build: 8-row tiles, the
         // per-wave y-row loads of k_st3d, the y-march k_st3y)
 #ifdef NK_KBENCH
-        if constexpr (kind_bratu(KIND)) {  // NK_BRATU3D: k_st3l only (launch_stencil_ex plans nothing else for it)
+        if constexpr (kind_of(KIND).bratu) {  // NK_BRATU3D: k_st3l only (launch_stencil_ex plans nothing else for it)
             if (A.nw == 8) return go_st3l<KIND, MODE, EPI, 8>(A, vec, grid, s, per);
         } else if (!A.blk) {  // (3D blocks: k_st3l with 4-row tiles only)
             if (A.ym) return A.nw == 8 ? go_st3y<KIND, MODE, EPI, 8>(A, vec, grid, s, per)

@@ -24,7 +24,7 @@ __global__ __launch_bounds__(64 * NW) void k_st2t(KArgs A0) {
     if constexpr (!kKeepVdiv && EPI != EPI_DOTV && EPI != EPI_DOTVS) A.vdiv = nullptr;  // v / h only with V_k stored
     A.hd = A.vdiv ? *A.vdiv : 1.0;
     A.ihd = 1.0 / A.hd;
-    constexpr int SCH = scheme_of<KIND>();
+    constexpr int SCH = kind_of(KIND).scheme;
     constexpr bool kG = SCH != 0 && MODE != MODE_JEXACT;
     constexpr bool kTG = SCH == 2 && kG;              // G_Trapezoid!: u_n's Laplacian
     constexpr bool kR = MODE == MODE_JFD && F0R;       // F0R: the u field as the residual kernel cooks it
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(64 * NW) void k_st3d(KArgs A0) {
     if constexpr (!kKeepVdiv && EPI != EPI_DOTV && EPI != EPI_DOTVS) A.vdiv = nullptr;  // v / h only with V_k stored
     A.hd = A.vdiv ? *A.vdiv : 1.0;
     A.ihd = 1.0 / A.hd;
-    constexpr int SCH = scheme_of<KIND>();
+    constexpr int SCH = kind_of(KIND).scheme;
     constexpr bool kG = SCH != 0 && MODE != MODE_JEXACT;
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(64 * NW) void k_st3y(KArgs A0) {
     if constexpr (!kKeepVdiv && EPI != EPI_DOTV && EPI != EPI_DOTVS) A.vdiv = nullptr;  // v / h only with V_k stored
     A.hd = A.vdiv ? *A.vdiv : 1.0;
     A.ihd = 1.0 / A.hd;
-    constexpr int SCH = scheme_of<KIND>();
+    constexpr int SCH = kind_of(KIND).scheme;
     constexpr bool kG = SCH != 0 && MODE != MODE_JEXACT;
     constexpr bool kTG = SCH == 2 && kG;
     constexpr bool kR = MODE == MODE_JFD && F0R;
@@ -599,7 +599,7 @@ StInst go_st2t(const KArgs& A, int vec, int grid, hipStream_t s, bool per) {
         constexpr int NWc = decltype(nwc)::value;
         const bool f0r = MODE == MODE_JFD && A.f0r;
         if (per) {
-            if constexpr (heat_kind<KIND>()) {
+            if constexpr (kind_of(KIND).heat) {
                 return f0r ? go_st2t_i<KIND, MODE, EPI, 2, true, true, NWc>(A, grid, s)
                            : go_st2t_i<KIND, MODE, EPI, 2, true, false, NWc>(A, grid, s);
             }

@@ -161,13 +161,16 @@ def test_supercritical_blows_up(scheme):
 
 # ----------------------------------------------------------------------------- the launch plan's trait
 def test_plan_header_has_no_f0r_for_the_kinds():
-    """csrc/nk_plan.hpp's st_kind_f0r (host code): false for 20 .. 22 -- no F0R instantiation exists, the launcher clears
-    the request and the FD launch reads F0 -- and true for every other built-in kind"""
-    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "newtonkrylov.jl_amd", "csrc")
-    src = '#include <cstdio>\n#include "nk_plan.hpp"\nint main() { for (int k = 1; k <= 24; ++k) std::printf("%d", nk::st_kind_f0r(k) ? 1 : 0); }\n'
+    """csrc/nk_kind.hpp's kind_of(k).f0r (host code; the launcher's question before it plans): false for 20 .. 22 -- no
+    F0R instantiation exists, the launcher clears the request and the FD launch reads F0 -- and true for every other
+    built-in stencil kind"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    inc = ["-I", os.path.join(root, "newtonkrylov.jl_amd", "csrc"), "-I", os.path.join(root, "include")]
+    src = ('#include <cstdio>\n#include "nk_kind.hpp"\n'
+           'int main() { for (int k : nk::kStencilKinds) std::printf("%d:%d ", k, nk::kind_of(k).f0r ? 1 : 0); }\n')
     with tempfile.TemporaryDirectory() as d:
         with open(os.path.join(d, "t.cpp"), "w") as fh:
             fh.write(src)
-        subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", csrc, "-o", os.path.join(d, "t"), os.path.join(d, "t.cpp")], check=True)
+        subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", *inc, "-o", os.path.join(d, "t"), os.path.join(d, "t.cpp")], check=True)
         out = subprocess.run([os.path.join(d, "t")], capture_output=True, text=True, check=True).stdout
-    assert out == "1" * 19 + "000" + "11"
+    assert out.split() == [f"{k}:1" for k in range(1, 10)] + ["20:0", "21:0", "22:0"]
