@@ -153,6 +153,13 @@ int nk_memcpy_d2h(nk_ctx* ctx, double* dst, const double* src, int64_t n);
 int nk_residual(nk_ctx* ctx, const nk_problem* p, double* res, const double* u);
 /* F!(res, u, p); n_res = norm(res)  fused into one pass (src/Ariadne.jl:302-303, :349-350). */
 int nk_residual_norm(nk_ctx* ctx, const nk_problem* p, double* res, const double* u, double* n_res);
+/* One trial of a line search: out = F(u + s v), *n_out = norm(out) (n_out may be null).  v is a grid function
+ * (nk_vec_alloc, or a workspace's x): its neighbours are read.  The built-in stencils form w = fma(s, v, u) in
+ * registers -- nk_axpy's expression -- under the residual launch's plan, so out and *n_out are bit for bit what
+ * nk_residual_norm gives on w = copy(u); nk_axpy(s, v, w), with 24 instead of 56 B/pt moved and no extra vector.
+ * NK_USER* kinds (and 3D blocks) materialise w in a scratch vector the context owns.  u and v are not written. */
+int nk_residual_trial(nk_ctx* ctx, const nk_problem* p, double* out, const double* u, const double* v, double s,
+                      double* n_out);
 /* mul!(out, J::JacobianOperator, v) (src/Ariadne.jl:48-57).  mode NK_JV_EXACT: the tangent of F!
  * (u, v read; F0 unused).  NK_JV_FD: (F(u + eps v) - F0)/eps with F0 = F(u); eps <= 0 selects
  * eps = sqrt(eps_mach) * max(1, ||u||) / ||v||.  Unlike Enzyme, `res` is not rewritten. */
@@ -365,6 +372,8 @@ int nk_krylov_solve(nk_workspace* ws, const nk_problem* p, const double* u, cons
 #define NK_FORCING_NONE 0   /* forcing = nothing: Krylov's own rtol                        */
 #define NK_FORCING_FIXED 1  /* Fixed(η), src/Ariadne.jl:185-192                             */
 #define NK_FORCING_EW 2     /* EisenstatWalker(η_max, γ), src/Ariadne.jl:197-217 (default)  */
+#define NK_LINESEARCH_NONE 0       /* the full Newton step u .-= d (src/Ariadne.jl:341-344; default) */
+#define NK_LINESEARCH_BACKTRACK 1  /* three-point parabolic backtracking (Kelley's nsoli)            */
 typedef struct nk_newton_opts {
     double tol_rel, tol_abs;      /* 1e-6, 1e-12: tol = tol_rel ||F(u0)|| + tol_abs            */
     int32_t max_niter;            /* 50 (the loop runs while outer <= max_niter, :336)         */
@@ -375,12 +384,23 @@ typedef struct nk_newton_opts {
     int32_t memory;               /* Krylov workspace memory (20)                              */
     nk_krylov_opts krylov;        /* krylov_kwargs; jv_mode selects the operator               */
     int32_t rtol_user;            /* krylov.rtol came from krylov_kwargs: it wins (:330-333)   */
+    /* line search on the Newton step (off by default: the loop is then exactly the reference's full step).
+       NK_LINESEARCH_BACKTRACK: Kelley's three-point parabolic backtracking on ||F|| -- accept lam when
+       ||F(u - lam d)|| < (1 - ls_alpha lam) ||F(u)||, else lam <- lam / 2 once, then the minimiser of the parabola
+       through the last two trials clamped to [ls_sigma0, ls_sigma1] lam; at most ls_maxarm reductions per step */
+    int32_t linesearch;           /* NK_LINESEARCH_NONE (0) / NK_LINESEARCH_BACKTRACK                 */
+    double ls_alpha, ls_sigma0, ls_sigma1;  /* 1e-4, 0.1, 0.5: 0 < alpha < 1, 0 < sigma0 <= sigma1 < 1 */
+    int32_t ls_maxarm;            /* 20 (>= 1)                                                  */
+    double* ls_hist;              /* optional host array: the accepted lam of every Newton step  */
+    int64_t ls_hist_cap;
 } nk_newton_opts;
 typedef struct nk_newton_stats {
     int64_t outer_iterations, inner_iterations;  /* Stats (src/Ariadne.jl:265-276)            */
     double n_res, tol;
     int32_t solved;               /* n_res <= tol (:370)                                       */
-    int64_t n_matvec, n_residual; /* mul!(J) and F! evaluations                                */
+    int64_t n_matvec, n_residual; /* mul!(J) and F! evaluations (line search: every trial is one) */
+    int64_t n_backtrack;          /* line search: rejected trials                              */
+    int32_t ls_failed;            /* line search: a step ran out of reductions (u is the last accepted iterate) */
 } nk_newton_stats;
 int nk_newton_defaults(nk_newton_opts* opts);
 /* nres_hist (optional, host): ||F|| after every Newton step, starting with ||F(u0)||. */

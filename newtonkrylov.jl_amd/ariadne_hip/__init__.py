@@ -4,7 +4,7 @@ Reference: vchuravy/NewtonKrylov.jl (package Ariadne.jl), src/Ariadne.jl.  The J
 1:1 with `!` -> trailing `_`:  newton_krylov! -> newton_krylov_, mul! -> mul_, kaxpy! -> kaxpy_.
 """
 from ._lib import NKError, device_count, load
-from .ariadne import (EisenstatWalker, Fixed, Forcing, JacobianOperator, Result, Stats, mul_, newton_krylov, newton_krylov_native, transpose, collect, TransposeOperator,
+from .ariadne import (Backtracking, EisenstatWalker, Fixed, Forcing, JacobianOperator, Result, Stats, mul_, newton_krylov, newton_krylov_native, transpose, collect, TransposeOperator,
                       newton_krylov_)
 from .device import Context, DeviceArray, Grid, default_context, set_default_context
 from .distributed import block, dist_unique_id, init_distributed, slab
@@ -18,7 +18,7 @@ from .problems import (DeviceResidual, UserResidual, bc_periodic_, bc_zero_, bra
                        ignition2d_trapezoid_)
 
 __all__ = [
-    "NKError", "device_count", "load", "EisenstatWalker", "Fixed", "Forcing", "JacobianOperator", "Result", "Stats",
+    "NKError", "device_count", "load", "Backtracking", "EisenstatWalker", "Fixed", "Forcing", "JacobianOperator", "Result", "Stats",
     "mul_", "newton_krylov", "newton_krylov_", "newton_krylov_native", "transpose", "collect", "TransposeOperator", "Context", "DeviceArray", "Grid", "default_context",
     "set_default_context", "dist_unique_id", "init_distributed", "slab", "block", "G_Euler_", "G_Midpoint_", "G_Trapezoid_", "diffusion_", "diffusion3d_", "solve",
     "KrylovConstructor", "exp_", "kaxpby_", "kaxpy_", "kaxpy_norm_", "kcopy_", "kdivcopy_", "kdot", "kfill_", "knorm", "kref_",

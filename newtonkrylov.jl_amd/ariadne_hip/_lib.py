@@ -83,17 +83,22 @@ class nk_krylov_stats(C.Structure):
 
 
 NK_FORCING_NONE, NK_FORCING_FIXED, NK_FORCING_EW = 0, 1, 2
+NK_LINESEARCH_NONE, NK_LINESEARCH_BACKTRACK = 0, 1
 
 
 class nk_newton_opts(C.Structure):
     _fields_ = [("tol_rel", C.c_double), ("tol_abs", C.c_double), ("max_niter", C.c_int32), ("forcing", C.c_int32),
                 ("eta", C.c_double), ("eta_max", C.c_double), ("gamma", C.c_double), ("algo", C.c_int32),
-                ("memory", C.c_int32), ("krylov", nk_krylov_opts), ("rtol_user", C.c_int32)]
+                ("memory", C.c_int32), ("krylov", nk_krylov_opts), ("rtol_user", C.c_int32),
+                ("linesearch", C.c_int32), ("ls_alpha", C.c_double), ("ls_sigma0", C.c_double),
+                ("ls_sigma1", C.c_double), ("ls_maxarm", C.c_int32), ("ls_hist", C.POINTER(C.c_double)),
+                ("ls_hist_cap", C.c_int64)]
 
 
 class nk_newton_stats(C.Structure):
     _fields_ = [("outer_iterations", C.c_int64), ("inner_iterations", C.c_int64), ("n_res", C.c_double),
-                ("tol", C.c_double), ("solved", C.c_int32), ("n_matvec", C.c_int64), ("n_residual", C.c_int64)]
+                ("tol", C.c_double), ("solved", C.c_int32), ("n_matvec", C.c_int64), ("n_residual", C.c_int64),
+                ("n_backtrack", C.c_int64), ("ls_failed", C.c_int32)]
 
 
 class nk_path_info(C.Structure):
@@ -128,6 +133,7 @@ SIGNATURES = {
     "nk_memcpy_d2h": (C.c_int, [_VP, _VP, _VP, _I64]),
     "nk_residual": (C.c_int, [_VP, _PP, _VP, _VP]),
     "nk_residual_norm": (C.c_int, [_VP, _PP, _VP, _VP, _PD]),
+    "nk_residual_trial": (C.c_int, [_VP, _PP, _VP, _VP, _VP, _D, _PD]),
     "nk_jv": (C.c_int, [_VP, _PP, _VP, _VP, _VP, _VP, _I32, _D]),
     "nk_jtv": (C.c_int, [_VP, _PP, _VP, _VP, _VP]),
     "nk_jv_batched": (C.c_int, [_VP, _PP, _I32, C.POINTER(_VP), _VP, C.POINTER(_VP), _VP, _I32, _D]),

@@ -59,6 +59,63 @@ class EisenstatWalker(Forcing):
         return self.eta_max
 
 
+# ----------------------------------------------------------------------------- line search
+@dataclass(frozen=True)
+class Backtracking:
+    """Backtracking(alpha = 1e-4, sigma0 = 0.1, sigma1 = 0.5, maxarm = 20): Kelley's three-point parabolic line
+    search on ‖F‖ for the Newton step -- the reference's `s = 1 # Newton step TODO: LineSearch` (src/Ariadne.jl:341).
+    λ is accepted when ‖F(u - λ d)‖ < (1 - alpha λ) ‖F(u)‖; the first reduction halves it (sigma1), the later ones
+    take the minimiser of the parabola through the last two trials, kept within [sigma0, sigma1] λ; a step that
+    rejects maxarm reductions fails.  The same operations in the same order as csrc/nk_linesearch.hpp (compared
+    with == by tests/test_linesearch_cpu.py)."""
+    alpha: float = 1.0e-4
+    sigma0: float = 0.1
+    sigma1: float = 0.5
+    maxarm: int = 20
+
+    def __post_init__(self):
+        if not self.maxarm >= 1:
+            raise ValueError("Backtracking: maxarm must be >= 1")
+        if not (0.0 < self.sigma0 <= self.sigma1 < 1.0):
+            raise ValueError("Backtracking: need 0 < sigma0 <= sigma1 < 1")
+        if not (0.0 < self.alpha < 1.0):
+            raise ValueError("Backtracking: need 0 < alpha < 1")
+
+    def parab3p(self, lc, lm, ff0, ffc, ffm):
+        """The next λ from the current / previous one (lc / lm) and ff = ‖F‖² at 0, lc, lm."""
+        if not (math.isfinite(ffc) and math.isfinite(ffm)):
+            return self.sigma1 * lc
+        c2 = lm * (ffc - ff0) - lc * (ffm - ff0)
+        if not c2 < 0.0:
+            return self.sigma1 * lc
+        c1 = lc * lc * (ffm - ff0) - lm * lm * (ffc - ff0)
+        lp = ((-c1) * 0.5) / c2
+        lo, hi = self.sigma0 * lc, self.sigma1 * lc
+        if not lp >= lo:
+            lp = lo
+        if lp > hi:
+            lp = hi
+        return lp
+
+    def search(self, n_res, trial):
+        """One Newton step: trial(s) evaluates ‖F(u + s d)‖.  Returns (λ, ‖F(u - λ d)‖, rejected trials); λ is None
+        when maxarm reductions were rejected (maxarm + 1 trials in all)."""
+        lam = lm = lc = 1.0
+        k = 0
+        n_t = trial(-lam)
+        ff0 = n_res * n_res
+        ffc = ffm = n_t * n_t
+        while not n_t < (1.0 - self.alpha * lam) * n_res:  # NaN and inf fail the test
+            if k == self.maxarm:
+                return None, n_t, k + 1
+            lam = self.sigma1 * lam if k == 0 else self.parab3p(lc, lm, ff0, ffc, ffm)
+            lm, lc, ffm = lc, lam, ffc
+            n_t = trial(-lam)
+            ffc = n_t * n_t
+            k += 1
+        return lam, n_t, k
+
+
 # ----------------------------------------------------------------------------- Jacobian operator
 class JacobianOperator:
     """JacobianOperator(F!, res, u, p) -- src/Ariadne.jl:34-46.
@@ -223,11 +280,15 @@ class Stats(NamedTuple):
 
 
 class Result(NamedTuple):
-    """(; solved, stats, t) -- src/Ariadne.jl:370-371 (+ n_matvec: mul!(J) calls of all Krylov solves)."""
+    """(; solved, stats, t) -- src/Ariadne.jl:370-371 (+ n_matvec: mul!(J) calls of all Krylov solves; with a line
+    search: n_backtrack rejected trials, ls_failed, steps = the accepted λ of every Newton step)."""
     solved: bool
     stats: Stats
     t: float
     n_matvec: int = 0
+    n_backtrack: int = 0
+    ls_failed: bool = False
+    steps: tuple = ()
 
 
 def _refreshed(P, J):
@@ -245,7 +306,7 @@ def newton_krylov_(F_: DeviceResidual, u: DeviceArray, p=None, res: DeviceArray 
                    tol_rel: float = 1.0e-6, tol_abs: float = 1.0e-12, max_niter: int = 50,
                    forcing: Forcing | None = EisenstatWalker(), verbose: int = 0, algo: str = "gmres",
                    M=None, N=None, krylov_kwargs: dict | None = None, callback=None, memory: int = 20,
-                   jv: str = "exact", workspace=None):
+                   jv: str = "exact", workspace=None, linesearch: Backtracking | None = None):
     """newton_krylov!(F!, u, p, res; kwargs...) -- src/Ariadne.jl:288-372 (and the 3-arg form :259-263).
 
     `N` (right) and `M` (left preconditioner) are preconditioner objects or factories `N(J)` /
@@ -255,9 +316,17 @@ def newton_krylov_(F_: DeviceResidual, u: DeviceArray, p=None, res: DeviceArray 
     Additions of the HIP path: `memory` (Krylov workspace memory = GMRES restart length),
     `jv` ("exact" | "fd") and `workspace` (re-use a Krylov workspace across calls -- the
     reference's own TODO at :316); everything else keeps the reference's meaning and default.
+    `linesearch` (None: the reference's full step, exactly today's loop) = Backtracking(...): the solve stores d,
+    every trial ‖F(u - λ d)‖ is one fused launch into res (residual_trial), the accepted step is kaxpy_norm_ --
+    the device calls of nk_newton_krylov's line-search branch, in its order.  A step that runs out of
+    reductions ends the loop with ls_failed (u the last accepted iterate, res = F(u)); callback fires once per
+    accepted step.
     """
+    from .krylov import kaxpy_norm_
     from .precond import multigrid
 
+    if linesearch is not None and not isinstance(linesearch, Backtracking):
+        raise TypeError("linesearch must be a Backtracking or None")
     callback = callback or (lambda *a: None)
     krylov_kwargs = dict(krylov_kwargs or {})
     # `N=multigrid` (the function itself): a factory of this solve's own, so its hierarchy goes with the solve
@@ -286,6 +355,7 @@ def newton_krylov_(F_: DeviceResidual, u: DeviceArray, p=None, res: DeviceArray 
     stats = Stats(0, 0, n_res)
     n_matvec = 0
     u_norm = 0.0  # ||u|| from the fused update below (the FD step size of the next solve); 0 = unknown
+    n_backtrack, ls_failed, steps = 0, False, []
     while n_res > tol and stats.outer_iterations <= max_niter:
         kwargs = dict(krylov_kwargs)
         if forcing is not None:
@@ -300,8 +370,30 @@ def newton_krylov_(F_: DeviceResidual, u: DeviceArray, p=None, res: DeviceArray 
             kwargs["N"] = _refreshed(N, J) if hasattr(N, "as_c") else N(J)
         if M is not None and "M" not in kwargs:
             kwargs["M"] = _refreshed(M, J) if hasattr(M, "as_c") else M(J)
-        krylov_solve_(workspace, J, res, _b_norm=n_res, _u_norm=u_norm, _u_update=u, _f0_is_residual=True, **kwargs)
+        krylov_solve_(workspace, J, res, _b_norm=n_res, _u_norm=u_norm, _u_update=u if linesearch is None else None,
+                      _f0_is_residual=True, **kwargs)
         n_matvec += workspace.stats.n_matvec
+        if linesearch is not None:
+            d = workspace.x
+            inner_rejected = workspace.stats.niter
+            lam, n_t, nrej = linesearch.search(n_res, lambda s_: F_.residual_trial(res, u, d, s_, p))
+            n_backtrack += nrej
+            if lam is None:  # u stays the last accepted iterate; res = F(u) again
+                ls_failed = True
+                n_res = F_.residual_norm(res, u, p)
+                stats = Stats(stats.outer_iterations, stats.inner_iterations + inner_rejected, n_res)
+                log.error("Line search failed after %d reductions: %s", linesearch.maxarm, stats)
+                break
+            u_norm = kaxpy_norm_(n, -lam, d, u)
+            steps.append(lam)
+            n_res_prior, n_res = n_res, n_t
+            callback(u, res, n_res)
+            if forcing is not None:
+                eta = forcing(eta, tol, n_res, n_res_prior)
+            stats = stats.update(workspace.stats.niter, n_res)
+            if verbose > 0:
+                log.info("Newton iter=%g eta=%s lam=%g %s", n_res, eta, lam, stats)
+            continue
         u_norm = workspace.stats.u_norm
         n_res_prior = n_res
         n_res = F_.residual_norm(res, u, p)
@@ -322,13 +414,14 @@ def newton_krylov_(F_: DeviceResidual, u: DeviceArray, p=None, res: DeviceArray 
     for f in own_factories:
         if f is not None:
             f.free()
-    return u, Result(n_res <= tol, stats, t, n_matvec)
+    return u, Result(n_res <= tol, stats, t, n_matvec, n_backtrack, ls_failed, tuple(steps))
 
 
 def newton_krylov_native(F_: DeviceResidual, u: DeviceArray, p=None, res: DeviceArray | None = None, *,
                          tol_rel: float = 1.0e-6, tol_abs: float = 1.0e-12, max_niter: int = 50,
                          forcing: Forcing | None = EisenstatWalker(), algo: str = "gmres",
-                         krylov_kwargs: dict | None = None, memory: int = 20, jv: str = "exact", N=None, M=None):
+                         krylov_kwargs: dict | None = None, memory: int = 20, jv: str = "exact", N=None, M=None,
+                         linesearch: Backtracking | None = None):
     """newton_krylov_ with the loop itself in libnkhip.so (nk_newton_krylov, the C/C++ callers' entry
     point).  Same arguments, same result; returns (u, Result) with the histories of ||F||.  N / M: a
     MultigridPreconditioner or the `multigrid` factory only (the C loop refreshes it from each step's u; with
@@ -389,8 +482,16 @@ def newton_krylov_native(F_: DeviceResidual, u: DeviceArray, p=None, res: Device
         o.krylov.N = C.cast(C.pointer(pcs["N"].as_c()), C.c_void_p)
     if "M" in pcs:
         o.krylov.M = C.cast(C.pointer(pcs["M"].as_c()), C.c_void_p)
-    st = _lib.nk_newton_stats()
     cap = int(max_niter) + 2
+    lsh = (C.c_double * cap)()
+    if linesearch is not None:
+        if not isinstance(linesearch, Backtracking):
+            raise TypeError("linesearch must be a Backtracking or None")
+        o.linesearch = _lib.NK_LINESEARCH_BACKTRACK
+        o.ls_alpha, o.ls_sigma0, o.ls_sigma1 = float(linesearch.alpha), float(linesearch.sigma0), float(linesearch.sigma1)
+        o.ls_maxarm = int(linesearch.maxarm)
+        o.ls_hist, o.ls_hist_cap = lsh, cap
+    st = _lib.nk_newton_stats()
     hist = (C.c_double * cap)()
     hl = C.c_int64(0)
     t0 = time.perf_counter_ns()
@@ -399,7 +500,8 @@ def newton_krylov_native(F_: DeviceResidual, u: DeviceArray, p=None, res: Device
                                         cap, C.byref(hl)), "nk_newton_krylov")
     t = (time.perf_counter_ns() - t0) / 1.0e9
     stats = Stats(int(st.outer_iterations), int(st.inner_iterations), float(st.n_res))
-    return u, Result(bool(st.solved), stats, t, int(st.n_matvec))
+    steps = tuple(lsh[: min(int(st.outer_iterations), cap)]) if linesearch is not None else ()
+    return u, Result(bool(st.solved), stats, t, int(st.n_matvec), int(st.n_backtrack), bool(st.ls_failed), steps)
 
 
 def newton_krylov(F, u0: DeviceArray, p=None, **kwargs):
@@ -407,7 +509,8 @@ def newton_krylov(F, u0: DeviceArray, p=None, **kwargs):
     modified.  F is a device residual (in place, as newton_krylov_ takes), or -- the reference's
     out-of-place `F(u, p)` that returns the residual -- a plain callable that gets u as a torch view
     and returns a tensor of u's shape; it is wrapped as F!(res, u, p) = (res .= F(u, p)) (:245-246),
-    a user residual without a tangent, so pass jv="fd"."""
+    a user residual without a tangent, so pass jv="fd".  linesearch=Backtracking(...) and every other keyword go to
+    newton_krylov_."""
     if not isinstance(F, DeviceResidual):
         if not callable(F):
             raise TypeError("newton_krylov: F must be a device residual or a callable F(u, p)")

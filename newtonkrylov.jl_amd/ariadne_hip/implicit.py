@@ -75,9 +75,10 @@ G_Trapezoid_ = _Scheme("G_Trapezoid!")
 
 
 def solve(G_, f_, un: DeviceArray, p, dt: float, ts, *, callback=None, verbose=0, algo="gmres",
-          krylov_kwargs=None, memory=20, jv="exact", stats_out=None, N=None, M=None):
+          krylov_kwargs=None, memory=20, jv="exact", stats_out=None, N=None, M=None, linesearch=None):
     """Non-adaptive implicit time stepping (implicit.jl:54-78).  Returns uₙ (updated in place).
-    N / M: newton_krylov_'s preconditioner keywords, handed to every step (e.g. N=multigrid)."""
+    N / M: newton_krylov_'s preconditioner keywords, handed to every step (e.g. N=multigrid); linesearch likewise
+    (Backtracking(...); None: the full Newton step)."""
     F_ = G_.bind(f_)
     callback = callback or (lambda u: None)
     u = un.copy()
@@ -87,7 +88,8 @@ def solve(G_, f_, un: DeviceArray, p, dt: float, ts, *, callback=None, verbose=0
     ts = list(ts)
     for t in ts[1:]:  # `if t == first(ts) continue`
         _, result = newton_krylov_(F_, u, (un, dt, du, p, t), res, verbose=verbose, algo=algo, tol_abs=6.0e-6,
-                                   krylov_kwargs=krylov_kwargs, memory=memory, jv=jv, workspace=ws, N=N, M=M)
+                                   krylov_kwargs=krylov_kwargs, memory=memory, jv=jv, workspace=ws, N=N, M=M,
+                                   linesearch=linesearch)
         if stats_out is not None:
             stats_out.append(result)
         if not result.solved:

@@ -52,6 +52,15 @@ class DeviceResidual:
         u.ctx.check(load().nk_residual_norm(u.ctx.handle, C.byref(prob), res.ptr, u.ptr, C.byref(out)), self.name)
         return out.value
 
+    def residual_trial(self, res: DeviceArray, u: DeviceArray, v: DeviceArray, s: float, p=None, *, norm: bool = True):
+        """res = F(u + s v) and its norm in one pass (nk_residual_trial): one trial of a line search.  Bit for bit
+        residual_norm on w = copy(u); kaxpy!(s, v, w), without the vector w.  norm=False: no reduction, returns None."""
+        prob = self.problem(u, p)
+        out = C.c_double()
+        u.ctx.check(load().nk_residual_trial(u.ctx.handle, C.byref(prob), res.ptr, u.ptr, v.ptr, float(s),
+                                             C.byref(out) if norm else None), self.name)
+        return out.value if norm else None
+
     def __repr__(self):
         return self.name
 

@@ -323,6 +323,29 @@ int nk_residual_norm(nk_ctx* c, const nk_problem* p, double* res, const double* 
     return host_scalar(c, r, 1, n_res);
 }
 
+// out = F(u + s v) and its norm: one trial of a line search.  The built-in stencils form w = fma(s, v, u) in registers
+// (MODE_TRIAL: nk_axpy's expression, the residual launch's plan), so out and *n_out are bit for bit what
+// nk_residual_norm gives on the materialised w.  User residuals and 3D blocks materialise w in the context's scratch.
+int nk_residual_trial(nk_ctx* c, const nk_problem* p, double* out, const double* u, const double* v, double s, double* n_out) {
+    if (!c || !out || !u || !v) return NK_E_ARG;
+    Geo g;
+    NK_TRY(geometry(c, p, &g));
+    if (kind_of(p->kind).user || blocks3d(c, g)) {
+        double* w = nullptr;
+        NK_TRY(user_scratch(c, p, g, &w));
+        NK_TRY(launch_copy(c, g.n, w, u));
+        NK_TRY(launch_axpy(c, g.n, s, v, w));
+        return n_out ? nk_residual_norm(c, p, out, w, n_out) : nk_residual(c, p, out, w);
+    }
+    NK_TRY(halo_exchange(c, p, u));
+    NK_TRY(halo_exchange(c, p, v));
+    NK_TRY(exchange_un(c, p));
+    StencilIn in{p, MODE_TRIAL, n_out ? EPI_SUMSQ : EPI_NONE, out, u, v, nullptr, nullptr, s};
+    Red r{};
+    NK_TRY(launch_stencil(c, in, &r));
+    return n_out ? host_scalar(c, r, 1, n_out) : NK_OK;
+}
+
 int nk_jv(nk_ctx* c, const nk_problem* p, double* out, const double* u, const double* v, const double* F0, int32_t mode,
           double eps) {
     if (!c || !out || !u || !v) return NK_E_ARG;

@@ -340,6 +340,9 @@ int launch_fd_point(nk_ctx* c, int64_t n, double* w, const double* u, const doub
 int launch_user_epi(nk_ctx* c, int64_t n, int fd, double* out, const double* F0, double eps, int epi,
                     const double* aux, Red* red);
 int launch_user(nk_ctx* c, const StencilIn& in, Red* red);  // nk_user.cpp
+// the context's scratch grid function (nk_user.cpp): the FD evaluation point of a user residual, and the
+// materialised trial point of nk_residual_trial; allocated on first use, freed with the context
+int user_scratch(nk_ctx* c, const nk_problem* p, const Geo& g, double** w);
 // nk_mg.hip: a multigrid preconditioner follows the Jacobian of each Newton step (nk_mg_set_jacobian), unless its
 // operator came from the caller (nk_mg_set_operator): then it is left as it is
 int mg_refresh(nk_mg* mg, const nk_problem* p, const double* u);

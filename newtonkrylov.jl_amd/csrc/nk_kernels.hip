@@ -612,6 +612,7 @@ double st_bytes(const StencilIn& in, int64_t n, const StInst& st) {
     int words = 1;  // out
     if (in.mode == MODE_RES) words += 1 + (un ? 1 : 0);
     else if (in.mode == MODE_JEXACT) words += 1 + (kind_of(kind).exp ? 1 : 0) + (jexact_reads_un(kind) ? 1 : 0);
+    else if (in.mode == MODE_TRIAL) words += 2 + (un ? 1 : 0);  // u, v
     else words += 3 + (un ? 1 : 0) - (st.f0r ? 1 : 0);
     if (in.epi == EPI_RESID || (in.epi == EPI_DOT && in.aux)) words += 1;
     if (in.vout) words += 1;  // fused kdivcopy!: V_k is written
@@ -620,11 +621,12 @@ double st_bytes(const StencilIn& in, int64_t n, const StInst& st) {
 
 // profile classes by mode and epilogue; normalise-and-store V_k and its V_1 = r0 / beta form, whose dot
 // partner is the stored vector itself, are distinct instantiations with profile lines of their own
-const char* const kStNames[3][4] = {{"residual", "residual_norm", "residual_dot", "residual_resid"},
+const char* const kStNames[4][4] = {{"residual", "residual_norm", "residual_dot", "residual_resid"},
                                     {"jv_exact", "jv_exact_sumsq", "jv_exact_dot", "jv_exact_resid"},
-                                    {"jv_fd", "jv_fd_sumsq", "jv_fd_dot", "jv_fd_resid"}};
-const char* const kStFusedNames[3] = {"residual", "jv_exact_dot_norm", "jv_fd_dot_norm"};
-const char* const kStV1Names[3] = {"residual", "jv_exact_dot_v1", "jv_fd_dot_v1"};
+                                    {"jv_fd", "jv_fd_sumsq", "jv_fd_dot", "jv_fd_resid"},
+                                    {"residual_trial", "residual_trial_norm", "residual_trial", "residual_trial"}};
+const char* const kStFusedNames[4] = {"residual", "jv_exact_dot_norm", "jv_fd_dot_norm", "residual_trial"};
+const char* const kStV1Names[4] = {"residual", "jv_exact_dot_v1", "jv_fd_dot_v1", "residual_trial"};
 }  // namespace
 
 int launch_stencil(nk_ctx* c, const StencilIn& in, Red* red) {
@@ -651,6 +653,13 @@ int launch_stencil_ex(nk_ctx* c, const StencilIn& in, Red* red, int rows_overrid
         knobs.vec_pref = 2;
         knobs.oneshot = 0;
         fast &= ~(4 | 8192 | 16384 | 32768 | 131072);
+    }
+    if (in.mode == MODE_TRIAL) {  // the trial residual has the product's kernels only: the residual launch's default plan
+        if (in.epi != EPI_NONE && in.epi != EPI_SUMSQ) return fail(c, NK_E_ARG, "trial residual: no epilogue but the norm");
+        if (blk) return fail(c, NK_E_ARG, "trial residual: 3D blocks take the materialised trial point");
+        knobs = StKnobs{};
+        fast = 0;
+        rows_override = 0;
     }
     const StPlan P = st_plan(StShape{g.dim, p->nx, p->ny, p->nz, per, blk, in.mode, kind_of(p->kind).heat, kind_of(p->kind).scheme,
                                      vstore, in.aux != nullptr, rows_override, fast, in.f0r && kind_of(p->kind).f0r},

@@ -6,11 +6,16 @@
 // krylov_kwargs carry rtol (:323-333), b = F(u) (:338; our operator never rewrites res, so res is
 // passed directly), u .-= d (:344), non-finite ||F|| ends the loop (:353-356), the forcing update
 // (:357-361) and Stats (:362-367).  Every O(n) step runs in this library on the device.
+//
+// opts->linesearch (off by default) fills the reference's `s = 1 # Newton step TODO: LineSearch` (:341): the solve
+// stores d, the step length comes from nk_linesearch.hpp's backtracking on the trial norms ||F(u - lam d)||
+// (nk_residual_trial writes each trial into res), and the accepted step is nk_axpy_norm.  DESIGN.md §14.
 #include <cfloat>
 #include <cmath>
 #include <vector>
 
 #include "nk_internal.hpp"
+#include "nk_linesearch.hpp"
 
 namespace {
 
@@ -42,6 +47,11 @@ int nk_newton_defaults(nk_newton_opts* o) {
     o->krylov.jv_mode = NK_JV_EXACT;
     o->krylov.atol = std::sqrt(DBL_EPSILON);
     o->krylov.rtol = std::sqrt(DBL_EPSILON);
+    const nk::LsOpts ls;  // linesearch stays NK_LINESEARCH_NONE
+    o->ls_alpha = ls.alpha;
+    o->ls_sigma0 = ls.sigma0;
+    o->ls_sigma1 = ls.sigma1;
+    o->ls_maxarm = ls.maxarm;
     return NK_OK;
 }
 
@@ -49,6 +59,19 @@ int nk_newton_krylov(nk_ctx* c, const nk_problem* p, double* u, double* res, con
                      nk_newton_stats* st, double* nres_hist, int64_t hist_cap, int64_t* hist_len) {
     if (!c || !p || !u || !res || !o || !st) return NK_E_ARG;
     if (o->forcing < NK_FORCING_NONE || o->forcing > NK_FORCING_EW) return nk::fail(c, NK_E_ARG, "bad forcing");
+    const bool ls = o->linesearch == NK_LINESEARCH_BACKTRACK;
+    nk::LsOpts lo;
+    if (o->linesearch != NK_LINESEARCH_NONE && !ls) return nk::fail(c, NK_E_ARG, "bad linesearch");
+    if (ls) {
+        lo.alpha = o->ls_alpha;
+        lo.sigma0 = o->ls_sigma0;
+        lo.sigma1 = o->ls_sigma1;
+        lo.maxarm = o->ls_maxarm;
+        if (!(lo.maxarm >= 1)) return nk::fail(c, NK_E_ARG, "linesearch: ls_maxarm must be >= 1");
+        if (!(lo.sigma0 > 0.0 && lo.sigma0 <= lo.sigma1 && lo.sigma1 < 1.0))
+            return nk::fail(c, NK_E_ARG, "linesearch: need 0 < ls_sigma0 <= ls_sigma1 < 1");
+        if (!(lo.alpha > 0.0 && lo.alpha < 1.0)) return nk::fail(c, NK_E_ARG, "linesearch: need 0 < ls_alpha < 1");
+    }
     nk::Geo g;
     NK_TRY(nk::geometry(c, p, &g));
     *st = nk_newton_stats{};
@@ -74,7 +97,8 @@ int nk_newton_krylov(nk_ctx* c, const nk_problem* p, double* u, double* res, con
         if (!o->rtol_user && o->forcing != NK_FORCING_NONE) ko.rtol = eta;
         ko.b_norm = n_res;  // b = F(u): its norm is the n_res just computed
         ko.u_norm = u_norm;
-        ko.u_update = u;    // u .-= d fused into the solve's last pass (d = workspace.x is not stored)
+        ko.u_update = ls ? nullptr : u;  // u .-= d fused into the solve's last pass (d = workspace.x is not stored);
+                                         // a line search needs d: the solve stores it
         ko.f0_is_residual = 1;  // res = F(u) was just computed by nk_residual_norm
         // a multigrid preconditioner follows the Jacobian: refresh its s = λ exp(u) (and the level diagonals);
         // one whose operator the caller set (nk_mg_set_operator) is left alone
@@ -89,6 +113,36 @@ int nk_newton_krylov(nk_ctx* c, const nk_problem* p, double* u, double* res, con
         const double* F0 = ko.jv_mode == NK_JV_FD ? res : nullptr;
         if ((rc = nk_krylov_solve(ws, p, u, F0, res, &ko, &ks, nullptr, 0, nullptr)) != NK_OK) break;
         st->n_matvec += ks.n_matvec;
+        if (ls) {  // u .-= lam .* d with lam from the backtracking; res receives every trial, the accepted one last
+            inner += ks.niter;
+            const double* d = nk_workspace_x(ws);
+            nk::LsStep S;
+            S.begin(lo, n_res);
+            double n_t = 0.0;
+            nk::LsVerdict v = nk::LS_RETRY;
+            for (;;) {
+                if ((rc = nk_residual_trial(c, p, res, u, d, -S.lam, &n_t)) != NK_OK) break;
+                st->n_residual++;
+                v = S.feed(n_t);
+                if (v == nk::LS_ACCEPT) break;
+                st->n_backtrack++;
+                if (v == nk::LS_FAILED) break;
+            }
+            if (rc != NK_OK) break;
+            if (v == nk::LS_FAILED) {  // u stays the last accepted iterate; res = F(u) again
+                st->ls_failed = 1;
+                if ((rc = nk_residual_norm(c, p, res, u, &n_res)) == NK_OK) st->n_residual++;
+                break;
+            }
+            if ((rc = nk_axpy_norm(c, g.n, -S.lam, d, u, &u_norm)) != NK_OK) break;
+            if (o->ls_hist && outer < o->ls_hist_cap) o->ls_hist[outer] = S.lam;
+            const double n_prior = n_res;
+            n_res = n_t;
+            if (o->forcing == NK_FORCING_EW) eta = ew_forcing(o->eta_max, o->gamma, eta, tol, n_res, n_prior);
+            outer += 1;
+            push(n_res);
+            continue;
+        }
         u_norm = ks.u_norm;  // ||u|| after u .-= 1 .* d (:344)
         const double n_prior = n_res;
         if ((rc = nk_residual_norm(c, p, res, u, &n_res)) != NK_OK) break;

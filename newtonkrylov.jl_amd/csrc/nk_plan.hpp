@@ -28,7 +28,9 @@ constexpr int kResTail = NK_RES_TAIL_DEFAULT;
 #define NK_F0R_DEFAULT 1
 #endif
 
-enum Mode { MODE_RES = 0, MODE_JEXACT = 1, MODE_JFD = 2 };
+// MODE_TRIAL: the residual at the trial point w = fma(s, v, u) of a line search (nk_residual_trial): the field is
+// loaded and cooked as MODE_JFD's, the value is MODE_RES's
+enum Mode { MODE_RES = 0, MODE_JEXACT = 1, MODE_JFD = 2, MODE_TRIAL = 3 };
 
 // ---------------------------------------------------------------- streaming grids
 // grid size of streaming reductions: >= 4 double2 per thread, at most `cap` (kMaxRedBlocks) blocks

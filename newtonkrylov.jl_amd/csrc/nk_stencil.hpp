@@ -127,9 +127,14 @@ __device__ __forceinline__ double fdq(const KArgs& A, double r, double f0c) {
     return div_rn(r - f0c, A.eps, A.ieps);
 }
 
+// MODE_TRIAL reads u and v as MODE_JFD does (KArgs::eps carries the step s) and evaluates MODE_RES's value
+constexpr bool reads_uv(int mode) { return mode == MODE_JFD || mode == MODE_TRIAL; }
+constexpr int value_mode(int mode) { return mode == MODE_TRIAL ? MODE_RES : mode; }
+
 template <int MODE>
 __device__ __forceinline__ double fieldval(const KArgs& A, int64_t o) {
     if (MODE == MODE_RES) return A.u[o];
+    if (MODE == MODE_TRIAL) return fma(A.eps, A.v[o], A.u[o]);  // w = u + s v: nk_axpy's expression
     if (MODE == MODE_JEXACT) return vin(A, o);
     return A.u[o] + A.eps * vin(A, o);  // w = u + eps v
 }
@@ -327,7 +332,7 @@ __global__ __launch_bounds__(kBlock) void k_st1d(KArgs A0) {
         const double uc = (MODE == MODE_JEXACT) ? A.u[i] : 0.0;
         const double f0 = (MODE == MODE_JFD) ? A.F0[i] : 0.0;
         bool rare_ = false;
-        double val = point_value<NK_BRATU1D, MODE>(A, c, lap(c, r, l, A.hx2), uc, 0.0, f0, c, 0.0, et, rare_);
+        double val = point_value<NK_BRATU1D, value_mode(MODE)>(A, c, lap(c, r, l, A.hx2), uc, 0.0, f0, c, 0.0, et, rare_);
         const double ax = (EPI == EPI_DOT || EPI == EPI_DOTV || EPI == EPI_RESID) ? A.aux[i]
                           : (EPI == EPI_DOTVS ? div_rn(A.v[i], A.hd, A.ihd) : 0.0);
         acc = epilogue<EPI>(val, ax, acc);
@@ -469,7 +474,7 @@ __device__ __forceinline__ RawRow<MODE, VEC> load_raw(const KArgs& A, int64_t o,
     if constexpr (EDGE) r.ae = pa[oe];
     else r.ae = 0.0;
     if constexpr (EDGE && PER) r.ae2 = e2 ? pa[oe2] : 0.0;
-    if constexpr (MODE == MODE_JFD) {
+    if constexpr (reads_uv(MODE)) {
         if constexpr (VEC % 2 == 0) {
 #pragma unroll
             for (int h = 0; h < VEC; h += 2) {
@@ -510,7 +515,7 @@ __device__ __forceinline__ RawRow<MODE, VEC> load_raw_ib(const KArgs& A, const u
     for (int h = 0; h < VEC; ++h) {
         if constexpr (MODE == MODE_JEXACT) r.a[h] = ld_inbox(ib + p + h);
         else r.a[h] = A.u[o + h];
-        if constexpr (MODE == MODE_JFD) r.b[h] = ld_inbox(ib + p + h);
+        if constexpr (reads_uv(MODE)) r.b[h] = ld_inbox(ib + p + h);
         if constexpr (G) r.g[h] = A.un[o + h];
     }
     r.ae = r.ae2 = 0.0;
@@ -557,6 +562,9 @@ __device__ __forceinline__ WV cook_w(const KArgs& A, double ra, double rb, bool 
     } else if constexpr (MODE == MODE_JEXACT) {
         r.v = div ? div_rn(ra, A.hd, A.ihd) : ra;
         r.w = r.v;
+    } else if constexpr (MODE == MODE_TRIAL) {
+        r.v = rb;
+        r.w = fma(A.eps, rb, ra);  // w = u + s v, bit for bit the vector nk_axpy(s, v, w = u) stores
     } else {
         r.v = div ? div_rn(rb, A.hd, A.ihd) : rb;
         r.w = ra + A.eps * r.v;  // w = u + eps v
@@ -579,7 +587,7 @@ __device__ __forceinline__ Field<VEC> cook(const KArgs& A, const RawRow<MODE, VE
     const bool div = A.vdiv != nullptr;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
-        const WV q = cook_w<MODE>(A, r.a[k], MODE == MODE_JFD ? r.b[k] : 0.0, div);
+        const WV q = cook_w<MODE>(A, r.a[k], reads_uv(MODE) ? r.b[k] : 0.0, div);
         const double w = q.w;
         f.vn[k] = q.v;
         f.x[k] = w;
@@ -590,11 +598,11 @@ __device__ __forceinline__ Field<VEC> cook(const KArgs& A, const RawRow<MODE, VE
             if constexpr (G) f.g[k] = 0.0;
         }
     }
-    const double e = mix<MODE, SCH>(A, cook_w<MODE>(A, r.ae, MODE == MODE_JFD ? r.be : 0.0, div).w, G ? r.ge : 0.0);
+    const double e = mix<MODE, SCH>(A, cook_w<MODE>(A, r.ae, reads_uv(MODE) ? r.be : 0.0, div).w, G ? r.ge : 0.0);
     f.e = edge_ok ? e : 0.0;
     if constexpr (G) f.ge = edge_ok ? r.ge : 0.0;
     if constexpr (PER) {
-        const double e2 = mix<MODE, SCH>(A, cook_w<MODE>(A, r.ae2, MODE == MODE_JFD ? r.be2 : 0.0, div).w, G ? r.ge2 : 0.0);
+        const double e2 = mix<MODE, SCH>(A, cook_w<MODE>(A, r.ae2, reads_uv(MODE) ? r.be2 : 0.0, div).w, G ? r.ge2 : 0.0);
         f.e2 = edge_ok2 ? e2 : 0.0;
         if constexpr (G) f.ge2 = edge_ok2 ? r.ge2 : 0.0;
     }

@@ -43,7 +43,7 @@ void k_st2d(KArgs A0) {
     // ghost rows of v from the neighbours' patches, fetched by this launch (tiles at the slab's ends)
     const uint64_t* ib_lo = nullptr;
     const uint64_t* ib_hi = nullptr;
-    if constexpr (MODE != MODE_RES && !PER) {
+    if constexpr (MODE != MODE_RES && MODE != MODE_TRIAL && !PER) {  // (a trial's ghost rows are exchanged first)
         const HaloTile ht{A.hx_lo && y0 == 0 && y0 < ny, A.hx_hi && y1 == ny && y0 < ny};
         if (ht.lo || ht.hi) {  // block-uniform
             const int64_t ca = (int64_t)tx * (kBlock * VEC), cb = ca + kBlock * VEC < nx ? ca + kBlock * VEC : nx;
@@ -151,7 +151,7 @@ void k_st2d(KArgs A0) {
                         const double lsu = lapk(A, ucc, ue, uw, A.hx2, A.ihx2) + lapk(A, ucc, up.c[k], um.c[k], A.hy2, A.ihy2);
                         f0 = point_value<KIND, MODE_RES, XM>(A, ucc, lsu, 0.0, unk, 0.0, SCH == 1 ? uc_.x[k] : ucc, lsumg, et, rare);
                     }
-                    double r = point_value<KIND, MODE, XM>(A, c, lsum, uc.v[k], unk, f0, SCH == 1 ? fc.x[k] : c, lsumg, et, rare);
+                    double r = point_value<KIND, value_mode(MODE), XM>(A, c, lsum, uc.v[k], unk, f0, SCH == 1 ? fc.x[k] : c, lsumg, et, rare);
                     acc = epilogue<EPI>(r, EPI == EPI_DOTVS ? fc.vn[k] : ax.v[k], acc);
                     val.v[k] = r;
                 }
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NK_ST3L
     // ghost planes of v from the neighbours' patches, fetched by this launch (z-tiles at the slab's ends)
     const uint64_t* ib_lo = nullptr;
     const uint64_t* ib_hi = nullptr;
-    if constexpr (MODE != MODE_RES && !PER && !BLK) {
+    if constexpr (MODE != MODE_RES && MODE != MODE_TRIAL && !PER && !BLK) {
         const HaloTile ht{A.hx_lo && z0 == 0 && z0 < nz, A.hx_hi && z1 == nz && z0 < nz};
         if (ht.lo || ht.hi) {  // block-uniform
             const int64_t ra = (int64_t)ty * NW, rb = ra + NW < ny ? ra + NW : ny;
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NK_ST3L
             }
         }
     }
-    if constexpr (MODE != MODE_RES && BLK) {
+    if constexpr (MODE != MODE_RES && MODE != MODE_TRIAL && BLK) {
         if (A.hx_blk) (void)blk_tile_exchange<NW, VEC>(A, tx, ty, tz, z0, z1, nzc);  // (a time-out is flagged)
     }
     double acc = 0.0;
@@ -609,7 +609,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NK_ST3L
                                            lapk(A, ucc, dn ? um.c[q] : up.c[q], dn ? up.c[q] : um.c[q], A.hz2, A.ihz2);
                         f0 = point_value<KIND, MODE_RES, XM>(A, ucc, lsu, 0.0, unq, 0.0, SCH == 1 ? uc_.x[q] : ucc, lsumg, et, rare_);
                     }
-                    double r = point_value<KIND, MODE, XM>(A, c, lsum, uc.v[q], unq, f0, SCH == 1 ? fc.x[q] : c, lsumg, et, rare_);
+                    double r = point_value<KIND, value_mode(MODE), XM>(A, c, lsum, uc.v[q], unq, f0, SCH == 1 ? fc.x[q] : c, lsumg, et, rare_);
                     acc = epilogue<EPI>(r, EPI == EPI_DOTVS ? fc.vn[q] : ax.v[q], acc);
                     val.v[q] = r;
                 }
@@ -767,6 +767,34 @@ StInst go_stencil(const KArgs& A, int vec, int grid, hipStream_t s, bool per) {
     }
 }
 
+// MODE_TRIAL (nk_residual_trial): the residual launch's kernels -- the 1D kernel, the VEC 1 / 2 row march, k_st3l with
+// 4-row tiles -- with the epilogues a line search uses (none, the sum of squares); no F0R, no 3D-block instance
+template <int KIND, int EPI>
+StInst go_stencil_trial_epi(const KArgs& A, int vec, int grid, hipStream_t s, bool per) {
+    if constexpr (kind_of(KIND).dim == 1) {
+        return go_st1d<MODE_TRIAL, EPI>(A, grid, s);
+    } else if constexpr (kind_of(KIND).dim == 2) {
+        if constexpr (kind_of(KIND).periodic) {
+            if (per) return vec == 2 ? go_st2d<KIND, MODE_TRIAL, EPI, 2, true>(A, grid, s)
+                                     : go_st2d<KIND, MODE_TRIAL, EPI, 1, true>(A, grid, s);
+        }
+        return vec == 2 ? go_st2d<KIND, MODE_TRIAL, EPI, 2>(A, grid, s) : go_st2d<KIND, MODE_TRIAL, EPI, 1>(A, grid, s);
+    } else {
+        if constexpr (kind_of(KIND).periodic) {
+            if (per) return vec == 2 ? go_st3l_i<KIND, MODE_TRIAL, EPI, 2, true, 4, false>(A, grid, s)
+                                     : go_st3l_i<KIND, MODE_TRIAL, EPI, 1, true, 4, false>(A, grid, s);
+        }
+        return vec == 2 ? go_st3l_i<KIND, MODE_TRIAL, EPI, 2, false, 4, false>(A, grid, s)
+                        : go_st3l_i<KIND, MODE_TRIAL, EPI, 1, false, 4, false>(A, grid, s);
+    }
+}
+
+template <int KIND>
+StInst go_stencil_trial(const KArgs& A, int epi, int vec, int grid, hipStream_t s, bool per) {
+    return epi == EPI_SUMSQ ? go_stencil_trial_epi<KIND, EPI_SUMSQ>(A, vec, grid, s, per)
+                            : go_stencil_trial_epi<KIND, EPI_NONE>(A, vec, grid, s, per);
+}
+
 template <int KIND, int MODE>
 StInst go_stencil_epi(const KArgs& A, int epi, int vec, int grid, hipStream_t s, bool per) {
     switch (epi) {
@@ -782,6 +810,7 @@ StInst go_stencil_epi(const KArgs& A, int epi, int vec, int grid, hipStream_t s,
 template <int KIND>
 StInst go_stencil_mode(const KArgs& A, int mode, int epi, int vec, int grid, hipStream_t s, bool per) {
     switch (mode) {
+    case MODE_TRIAL: return go_stencil_trial<KIND>(A, epi, vec, grid, s, per);
     case MODE_RES: return go_stencil_epi<KIND, MODE_RES>(A, epi, vec, grid, s, per);
     case MODE_JEXACT: return go_stencil_epi<KIND, MODE_JEXACT>(A, epi, vec, grid, s, per);
     default: return go_stencil_epi<KIND, MODE_JFD>(A, epi, vec, grid, s, per);

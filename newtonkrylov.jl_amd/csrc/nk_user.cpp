@@ -18,7 +18,7 @@
 namespace nk {
 
 // FD evaluation point, allocated like any grid function of this geometry and kept on the context
-static int user_scratch(nk_ctx* c, const nk_problem* p, const Geo& g, double** w) {
+int user_scratch(nk_ctx* c, const nk_problem* p, const Geo& g, double** w) {
     if (!c->user_w || c->user_w_n != g.n || c->user_w_plane != g.plane) {
         if (c->user_w) NK_TRY(nk_vec_free(c, c->user_w));
         c->user_w = nullptr;

@@ -3,6 +3,11 @@
 // Eisenstat-Walker forcing (src/Ariadne.jl:288-372), FD or exact Jv.  Prints one JSON line.
 //
 //   bin/bratu2d_newton [N=256] [NY] [jv=fd|exact] [memory=30] [restart=1] [--mg] [--mg-semi] [--cg] [--minres]
+//                      [--linesearch] [--lambda L] [--amp A] [--no-forcing]
+// --linesearch: backtracking on the Newton step (NK_LINESEARCH_BACKTRACK); the JSON line then carries "linesearch",
+// "n_backtrack", "ls_failed" and "steps" (the accepted step lengths).  --lambda L: Bratu's λ (default 3.51382);
+// --amp A: u0 = A sin sin (default 1); --no-forcing: Krylov's own rtol instead of Eisenstat-Walker -- together a
+// start from which the full step overshoots (e.g. 24 20 exact 480 --lambda 1 --amp 5 --no-forcing --linesearch).
 // NY (a number right after N): an N x NY grid on the unit square (h_x != h_y); the JSON line then carries "ny".
 // --mg (anywhere on the line): the geometric multigrid V-cycle as the right preconditioner N (NK_PRECOND_MG).
 // --mg-semi (implies --mg): the hierarchy on the semicoarsened plan (nk_mg_plan_semi / nk_mg_create_levels), for
@@ -30,13 +35,18 @@
     } while (0)
 
 int main(int argc, char** argv) {
-    bool use_mg = false, use_cg = false, use_minres = false, semi = false;
+    bool use_mg = false, use_cg = false, use_minres = false, semi = false, linesearch = false, no_forcing = false;
+    double lambda = 3.51382, amp = 1.0;  // examples/bratu.jl:41-42
     int nargs = 1;
     for (int i = 1; i < argc; ++i) {  // strip --mg / --mg-semi / --cg / --minres, keep the positional arguments
         if (std::strcmp(argv[i], "--mg") == 0) use_mg = true;
         else if (std::strcmp(argv[i], "--mg-semi") == 0) use_mg = semi = true;
         else if (std::strcmp(argv[i], "--cg") == 0) use_cg = true;
         else if (std::strcmp(argv[i], "--minres") == 0) use_minres = true;
+        else if (std::strcmp(argv[i], "--linesearch") == 0) linesearch = true;
+        else if (std::strcmp(argv[i], "--no-forcing") == 0) no_forcing = true;
+        else if (std::strcmp(argv[i], "--lambda") == 0 && i + 1 < argc) lambda = std::atof(argv[++i]);
+        else if (std::strcmp(argv[i], "--amp") == 0 && i + 1 < argc) amp = std::atof(argv[++i]);
         else argv[nargs++] = argv[i];
     }
     argc = nargs;
@@ -51,7 +61,7 @@ int main(int argc, char** argv) {
     const bool fd = argc > 2 ? std::strcmp(argv[2], "exact") != 0 : true;
     const int memory = argc > 3 ? std::atoi(argv[3]) : 30;
     const int restart = argc > 4 ? std::atoi(argv[4]) : 1;
-    const double h = 1.0 / (double)(N + 1), hy = 1.0 / (double)(NY + 1), lambda = 3.51382;  // examples/bratu.jl:41-42
+    const double h = 1.0 / (double)(N + 1), hy = 1.0 / (double)(NY + 1);
 
     nk_ctx* ctx = nullptr;
     if (nk_ctx_create(0, &ctx) != NK_OK) {
@@ -73,7 +83,7 @@ int main(int argc, char** argv) {
     CHECK(ctx, nk_vec_alloc(ctx, &p, &res));
     std::vector<double> host((size_t)(N * NY));
     for (int64_t j = 0; j < NY; ++j)
-        for (int64_t i = 0; i < N; ++i) host[(size_t)(j * N + i)] = std::sin(M_PI * (i + 1) * h) * std::sin(M_PI * (j + 1) * hy);
+        for (int64_t i = 0; i < N; ++i) host[(size_t)(j * N + i)] = amp * (std::sin(M_PI * (i + 1) * h) * std::sin(M_PI * (j + 1) * hy));
     CHECK(ctx, nk_memcpy_h2d(ctx, u, host.data(), N * NY));
 
     nk_newton_opts o;
@@ -115,6 +125,13 @@ int main(int argc, char** argv) {
             o.krylov.N = &Nmg;
         }
     }
+    double steps[64];
+    if (linesearch) {
+        o.linesearch = NK_LINESEARCH_BACKTRACK;
+        o.ls_hist = steps;
+        o.ls_hist_cap = 64;
+    }
+    if (no_forcing) o.forcing = NK_FORCING_NONE;
     nk_newton_stats st;
     double hist[64];
     int64_t nh = 0;
@@ -134,7 +151,14 @@ int main(int argc, char** argv) {
                 st.solved ? "true" : "false", (long long)st.outer_iterations,
                 (long long)st.inner_iterations, (long long)st.n_matvec, st.n_res, st.tol, umax, secs);
     for (int64_t k = 0; k < nh && k < 64; ++k) std::printf("%s%.17g", k ? ", " : "", hist[k]);
-    std::printf("]}\n");
+    std::printf("]");
+    if (linesearch) {
+        std::printf(", \"linesearch\": true, \"n_backtrack\": %lld, \"ls_failed\": %s, \"steps\": [", (long long)st.n_backtrack,
+                    st.ls_failed ? "true" : "false");
+        for (int64_t k = 0; k < st.outer_iterations && k < 64; ++k) std::printf("%s%.17g", k ? ", " : "", steps[k]);
+        std::printf("]");
+    }
+    std::printf("}\n");
     if (mg) CHECK(ctx, nk_mg_destroy(mg));
     CHECK(ctx, nk_vec_free(ctx, u));
     CHECK(ctx, nk_vec_free(ctx, res));

@@ -3,7 +3,9 @@
 // newton_krylov! with GMRES(memory) and the Eisenstat-Walker forcing (src/Ariadne.jl:288-372), FD or exact Jv.
 // Prints one JSON line, the one bratu2d_newton prints (with "ny" and "nz" when they are given).
 //
-//   bin/bratu3d_newton [NX=64] [NY NZ] [jv=fd|exact] [memory=30] [restart=1] [--lambda L] [--mg] [--mg-semi] [--cg] [--minres]
+//   bin/bratu3d_newton [NX=64] [NY NZ] [jv=fd|exact] [memory=30] [restart=1] [--lambda L] [--mg] [--mg-semi] [--cg] [--minres] [--linesearch]
+// --linesearch: backtracking on the Newton step (NK_LINESEARCH_BACKTRACK); the JSON line then carries "linesearch",
+// "n_backtrack", "ls_failed" and "steps" (the accepted step lengths).
 // NY NZ (two numbers right after NX): an NX x NY x NZ grid, h_a = 1 / (n_a + 1); without them NX^3.
 // --lambda L: Bratu's λ (default 3.51382, examples/bratu.jl:42; the 3D fold is near 9.9).
 // --mg (anywhere on the line): the geometric multigrid V-cycle as the right preconditioner N (NK_PRECOND_MG).
@@ -32,7 +34,7 @@
 static bool digits(const char* s) { return s[0] != '\0' && std::strspn(s, "0123456789") == std::strlen(s); }
 
 int main(int argc, char** argv) {
-    bool use_mg = false, use_cg = false, use_minres = false, semi = false;
+    bool use_mg = false, use_cg = false, use_minres = false, semi = false, linesearch = false;
     double lambda = 3.51382;  // examples/bratu.jl:42
     int nargs = 1;
     for (int i = 1; i < argc; ++i) {  // strip the options, keep the positional arguments
@@ -40,6 +42,7 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[i], "--mg-semi") == 0) use_mg = semi = true;
         else if (std::strcmp(argv[i], "--cg") == 0) use_cg = true;
         else if (std::strcmp(argv[i], "--minres") == 0) use_minres = true;
+        else if (std::strcmp(argv[i], "--linesearch") == 0) linesearch = true;
         else if (std::strcmp(argv[i], "--lambda") == 0 && i + 1 < argc) lambda = std::atof(argv[++i]);
         else argv[nargs++] = argv[i];
     }
@@ -130,6 +133,12 @@ int main(int argc, char** argv) {
             o.krylov.N = &Nmg;
         }
     }
+    double steps[64];
+    if (linesearch) {
+        o.linesearch = NK_LINESEARCH_BACKTRACK;
+        o.ls_hist = steps;
+        o.ls_hist_cap = 64;
+    }
     nk_newton_stats st;
     double hist[64];
     int64_t nh = 0;
@@ -149,7 +158,14 @@ int main(int argc, char** argv) {
                 st.solved ? "true" : "false", (long long)st.outer_iterations,
                 (long long)st.inner_iterations, (long long)st.n_matvec, st.n_res, st.tol, umax, secs);
     for (int64_t k = 0; k < nh && k < 64; ++k) std::printf("%s%.17g", k ? ", " : "", hist[k]);
-    std::printf("]}\n");
+    std::printf("]");
+    if (linesearch) {
+        std::printf(", \"linesearch\": true, \"n_backtrack\": %lld, \"ls_failed\": %s, \"steps\": [", (long long)st.n_backtrack,
+                    st.ls_failed ? "true" : "false");
+        for (int64_t k = 0; k < st.outer_iterations && k < 64; ++k) std::printf("%s%.17g", k ? ", " : "", steps[k]);
+        std::printf("]");
+    }
+    std::printf("}\n");
     if (mg) CHECK(ctx, nk_mg_destroy(mg));
     CHECK(ctx, nk_vec_free(ctx, u));
     CHECK(ctx, nk_vec_free(ctx, res));

@@ -6,6 +6,9 @@
 // solution blows up in finite time and the steps stop being solved.
 //
 //   bin/ignition2d_solve NX [NY] [euler|midpoint|trapezoid] [--lambda L] [--a A] [--dt DT] [--steps K] [--alpha AL] [--mg] [--fd]
+//                       [--linesearch]
+// --linesearch: backtracking on every Newton step (NK_LINESEARCH_BACKTRACK); each step's line then ends with
+// " backtracks B ls_failed F".
 // One line per step: step, Newton steps, Krylov steps, ||F||, max u, solved.  The exit status is 0 even when a step
 // is not solved (the reference warns and marches on); non-zero only when a library call fails.
 // --mg: the geometric multigrid V-cycle as the right preconditioner N, refreshed from J(u) in every Newton step.
@@ -30,12 +33,13 @@
 static bool digits(const char* s) { return s[0] != '\0' && std::strspn(s, "0123456789") == std::strlen(s); }
 
 int main(int argc, char** argv) {
-    bool use_mg = false, fd = false;
+    bool use_mg = false, fd = false, linesearch = false;
     double lambda = 3.51382, a = 1.0, dt = 0.05, alpha = 0.5;
     int steps = 10, nargs = 1;
     for (int i = 1; i < argc; ++i) {  // strip the options, keep the positional arguments
         if (std::strcmp(argv[i], "--mg") == 0) use_mg = true;
         else if (std::strcmp(argv[i], "--fd") == 0) fd = true;
+        else if (std::strcmp(argv[i], "--linesearch") == 0) linesearch = true;
         else if (std::strcmp(argv[i], "--lambda") == 0 && i + 1 < argc) lambda = std::atof(argv[++i]);
         else if (std::strcmp(argv[i], "--a") == 0 && i + 1 < argc) a = std::atof(argv[++i]);
         else if (std::strcmp(argv[i], "--dt") == 0 && i + 1 < argc) dt = std::atof(argv[++i]);
@@ -96,6 +100,7 @@ int main(int argc, char** argv) {
     CHECK(ctx, nk_newton_defaults(&o));
     o.tol_abs = 6.0e-6;  // implicit.jl:61
     o.krylov.jv_mode = fd ? NK_JV_FD : NK_JV_EXACT;
+    if (linesearch) o.linesearch = NK_LINESEARCH_BACKTRACK;
     nk_mg* mg = nullptr;
     nk_precond Nmg{};
     if (use_mg) {
@@ -115,8 +120,10 @@ int main(int argc, char** argv) {
             ++unsolved;
             std::fprintf(stderr, "non linear solve failed marching on t=%.17g\n", k * dt);
         }
-        std::printf("step %d newton %lld krylov %lld n_res %.6e u_max %.6e solved %d\n", k, (long long)st.outer_iterations,
+        std::printf("step %d newton %lld krylov %lld n_res %.6e u_max %.6e solved %d", k, (long long)st.outer_iterations,
                     (long long)st.inner_iterations, st.n_res, umax, st.solved ? 1 : 0);
+        if (linesearch) std::printf(" backtracks %lld ls_failed %d", (long long)st.n_backtrack, (int)st.ls_failed);
+        std::printf("\n");
         CHECK(ctx, nk_memcpy_h2d(ctx, un, host.data(), n));  // u_n .= u
     }
     if (unsolved) std::fprintf(stderr, "%d of %d steps not solved\n", unsolved, steps);

@@ -646,4 +646,91 @@ function Krylov.krylov_solve!(ws::HipKrylovWorkspace, J::HipJacobian, b::HipVect
     return ws
 end
 
+# --------------------------------------------------------------------------- Newton step with a line search
+# Ariadne takes the full step (`s = 1 # Newton step TODO: LineSearch`, src/Ariadne.jl:341).  newton_krylov_ls! is its
+# loop with that line filled in: Kelley's three-point parabolic backtracking (csrc/nk_linesearch.hpp, the same
+# operations in the same order), every trial ||F(u - λ d)|| one fused launch (nk_residual_trial).
+"""`res .= F(u + s v)` and its norm in one pass; bit for bit `F!` on `w = copy(u); kaxpy!(n, s, v, w)`."""
+function residual_trial!(F::AnyHipResidual, res::HipVector, u::HipVector, v::HipVector, s::Real, p)
+    r = Ref{Float64}()
+    check(ccall((:nk_residual_trial, libnkhip), Cint,
+                (VP, Ref{NkProblem}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Ref{Float64}),
+                u.ctx.ptr, problem(F, u, p), res.ptr, u.ptr, v.ptr, Float64(s), r), u.ctx, "residual_trial!")
+    touch!(res)
+    return r[]
+end
+
+Base.@kwdef struct Backtracking
+    alpha::Float64 = 1e-4
+    sigma0::Float64 = 0.1
+    sigma1::Float64 = 0.5
+    maxarm::Int = 20
+end
+
+function parab3p(ls::Backtracking, lc, lm, ff0, ffc, ffm)
+    (isfinite(ffc) && isfinite(ffm)) || return ls.sigma1 * lc
+    c2 = lm * (ffc - ff0) - lc * (ffm - ff0)
+    c2 < 0 || return ls.sigma1 * lc
+    c1 = lc * lc * (ffm - ff0) - lm * lm * (ffc - ff0)
+    lp = ((-c1) * 0.5) / c2
+    lo, hi = ls.sigma0 * lc, ls.sigma1 * lc
+    lp >= lo || (lp = lo)
+    lp > hi && (lp = hi)
+    return lp
+end
+
+"""newton_krylov!(F!, u, p, res; ...) with `linesearch = Backtracking()` (`nothing`: Ariadne's own loop).  Returns
+`(u, (; solved, stats, steps, n_backtrack, ls_failed))`."""
+function newton_krylov_ls!(F!::AnyHipResidual, u::HipVector, p, res::HipVector = similar(u);
+                           linesearch::Union{Nothing, Backtracking} = Backtracking(), tol_rel = 1e-6, tol_abs = 1e-12,
+                           max_niter = 50, forcing::Union{Nothing, Ariadne.Forcing} = Ariadne.EisenstatWalker(),
+                           algo = :gmres, memory::Integer = 20, krylov_kwargs = (;), kwargs...)
+    linesearch === nothing && return Ariadne.newton_krylov!(F!, u, p, res; tol_rel, tol_abs, max_niter, forcing, algo,
+                                                            krylov_kwargs, kwargs...)
+    ls = linesearch
+    (ls.maxarm >= 1 && 0 < ls.sigma0 <= ls.sigma1 < 1 && 0 < ls.alpha < 1) || error("Backtracking: invalid options")
+    F!(res, u, p)
+    n_res = norm(res)
+    tol = tol_rel * n_res + tol_abs
+    η = forcing === nothing ? nothing : Ariadne.inital(forcing)
+    J = Ariadne.JacobianOperator(F!, res, u, p)
+    ws = Krylov.krylov_workspace(algo, KrylovConstructor(res); memory)
+    stats = Ariadne.Stats(0, 0, n_res)
+    steps, n_backtrack, ls_failed = Float64[], 0, false
+    while n_res > tol && stats.outer_iterations <= max_niter
+        kw = forcing === nothing ? krylov_kwargs : (; rtol = η, krylov_kwargs...)
+        Krylov.krylov_solve!(ws, J, res; kw...)  # d = ws.x; res = F(u) is untouched until the first trial
+        d = ws.x
+        lam = lm = lc = 1.0
+        k = 0
+        n_t = residual_trial!(F!, res, u, d, -lam, p)
+        ff0 = n_res * n_res
+        ffc = ffm = n_t * n_t
+        while !(n_t < (1.0 - ls.alpha * lam) * n_res)
+            n_backtrack += 1
+            if k == ls.maxarm
+                ls_failed = true
+                break
+            end
+            lam = k == 0 ? ls.sigma1 * lam : parab3p(ls, lc, lm, ff0, ffc, ffm)
+            lm, lc, ffm = lc, lam, ffc
+            n_t = residual_trial!(F!, res, u, d, -lam, p)
+            ffc = n_t * n_t
+            k += 1
+        end
+        if ls_failed  # u stays the last accepted iterate; res = F(u) again
+            F!(res, u, p)
+            stats = Ariadne.Stats(stats.outer_iterations, stats.inner_iterations + ws.stats.niter, n_res)
+            break
+        end
+        kaxpy!(length(u), -lam, d, u)
+        res.f0of = F! isa HipResidual ? f0stamp(u, p) : nothing  # the accepted trial is F(u) at the updated u
+        push!(steps, lam)
+        n_res_prior, n_res = n_res, n_t
+        forcing === nothing || (η = forcing(η, tol, n_res, n_res_prior))
+        stats = Ariadne.update(stats, ws.stats.niter, n_res)
+    end
+    return u, (; solved = n_res <= tol, stats, steps, n_backtrack, ls_failed)
+end
+
 end # module
