@@ -11,6 +11,7 @@ Tolerances (stated per test):
     converged solutions to the stated solver tolerance.
 """
 import json
+import math
 import os
 
 import numpy as np
@@ -18,6 +19,7 @@ import pytest
 
 import _nkpath  # noqa: F401
 import ariadne_hip as ah
+from bratu3d_ref import reduction_bound
 from oracle import oracle as oc
 
 pytestmark = pytest.mark.gpu
@@ -122,6 +124,16 @@ def test_blas1_parity(ctx, n):
     assert abs(ah.knorm(n, xd) - np.linalg.norm(x)) <= 1e-13 * np.linalg.norm(x)
     s, t = 0.37, -1.25
     assert np.array_equal(ah.kaxpy_(n, s, xd, yd.copy()).to_numpy(), oc.axpy(s, x, y))
+    # the fused Newton update (k_axpy_sumsq): the vector is kaxpy!'s, its norm any-order sum of squares -- within
+    # n 2^-53 sum|terms| of fsum, carried through the square root (monotone, one rounding)
+    yn = yd.copy()
+    nrm = ah.kaxpy_norm_(n, s, xd, yn)
+    z = oc.axpy(s, x, y)
+    assert np.array_equal(yn.to_numpy(), z)
+    S, B = reduction_bound(z * z)
+    lo, hi = math.sqrt(max(S - B, 0.0)) * (1 - 2.0 ** -52), math.sqrt(S + B) * (1 + 2.0 ** -52)
+    print(f"n {n}: ||s x + y|| {nrm:.17g}, sqrt(fsum) {math.sqrt(S):.17g}, allowed [{lo:.17g}, {hi:.17g}]")
+    assert lo <= nrm <= hi
     assert np.array_equal(ah.kaxpby_(n, s, xd, t, yd.copy()).to_numpy(), oc.axpby(s, x, t, y))
     assert np.array_equal(ah.kscal_(n, s, xd.copy()).to_numpy(), s * x)
     assert np.array_equal(ah.kdivcopy_(n, yd.copy(), xd, 3.0).to_numpy(), x / 3.0)

@@ -263,10 +263,13 @@ _BC = {oc.BC_ZERO: ah.bc_zero_, oc.BC_PERIODIC: ah.bc_periodic_}
 @pytest.mark.parametrize("scheme,alpha,bc,shape", [
     ("euler", 0.5, oc.BC_ZERO, (256, 192)),
     ("trapezoid", 0.5, oc.BC_PERIODIC, (256, 256)),     # k_st2d's periodic instance (square: heat_2D.jl:23-24)
-    ("midpoint", 0.3, oc.BC_ZERO, (130, 67)),           # odd width: one-column (VEC 1) tiles
+    ("midpoint", 0.3, oc.BC_ZERO, (130, 67)),           # even width (VEC 2), the last wave holds two columns
     ("euler", 0.5, oc.BC_ZERO, (64, 48, 40)),           # k_st3l's tiles, z-chunks
     ("midpoint", 0.5, oc.BC_PERIODIC, (48, 48, 48)),
     ("trapezoid", 0.5, oc.BC_ZERO, (66, 33, 20)),
+    # (new cases go last: the test ids carry the position)
+    ("midpoint", 0.3, oc.BC_ZERO, (129, 67)),           # odd width: one-column (VEC 1) tiles
+    ("euler", 0.5, oc.BC_ZERO, (65, 33, 20)),           # 3D with an odd width: VEC 1, two x-tiles, two z-chunks
 ])
 def test_scheme_newton_bitwise_in_device_order(ctx, scheme, alpha, bc, shape):
     """One implicit step of each implicit.jl scheme (G_Euler! / G_Midpoint!(α) / G_Trapezoid! over diffusion!,
