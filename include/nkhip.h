@@ -86,7 +86,8 @@ extern "C" {
                               nk_ilu0_factor.  Distributed: block Jacobi (each slab factored on its own) */
 #define NK_PRECOND_MG 5    /* z = one geometric multigrid V-cycle on v, from x = 0 (a fixed linear map: valid for
                               NK_ALGO_GMRES as well as NK_ALGO_FGMRES); data = the nk_mg handle (nk_mg_create).
-                              Built-in stencil kinds, bc_zero!, one rank */
+                              Built-in stencil kinds with bc_zero! (one rank, or slabs on a distributed context);
+                              the heat kinds with bc_periodic! on one rank */
 typedef int (*nk_user_precond)(void* data, struct nk_ctx* ctx, double* out, const double* in);
 typedef struct nk_precond {
     int32_t kind;          /* NK_PRECOND_*                                   */
@@ -283,7 +284,20 @@ typedef struct nk_mg_opts {
 /* the level extents of a grid (host only, no GPU): extents[3 l + a] = n_a of level l (1 for unused axes),
  * at most cap levels written, *nlevels = the number of levels */
 int nk_mg_plan(const int64_t n[3], int32_t max_levels, int64_t* extents, int32_t cap, int32_t* nlevels);
-/* opts may be null (the defaults).  NK_E_ARG for periodic boundaries and NK_USER* kinds.
+/* the plan of a periodic grid (host only, no GPU; output as nk_mg_plan).  The levels are nested (coarse point j is
+ * fine point 2 j), so an axis is halved while it is even and has at least 6 points (n / 2 >= 3 remain); the others are
+ * kept, and the plan ends when no axis can be halved.  Extents of the form (3, 4 or 5) 2^k are the intended ones: an
+ * odd axis is never coarsened, and point Jacobi then smooths badly along it (valid but weak).  NK_E_ARG where a used
+ * axis has fewer than 3 points. */
+int nk_mg_plan_periodic(const int64_t n[3], int32_t max_levels, int64_t* extents, int32_t cap, int32_t* nlevels);
+/* opts may be null (the defaults).  NK_E_ARG for NK_USER* kinds.
+ *
+ * p->bc == NK_BC_PERIODIC: the hierarchy of a periodic grid, for the heat kinds (NK_HEAT2D_* / NK_HEAT3D_*) on one
+ * rank.  Its levels are nk_mg_plan_periodic's; neighbours and transfers wrap, the coarse operators are rediscretised
+ * with h_a^l = h_a^0 (n_a^0 / n_a^l) (the period stays), P takes e_c[i / 2] at an even fine i and the mean of its two
+ * coarse neighbours at an odd one, R = D^-1 P^T has the weights 1, 2, 1 over D = 4 per coarsened axis; smoother,
+ * cycle, sign check, SPD form and nk_mg_set_operator are unchanged.  NK_E_ARG naming "periodic" for
+ * everything else periodic: Bratu and ignition kinds, a distributed context, nk_mg_create_levels.
  *
  * On a distributed context (nk_dist_init / nk_dist_mailbox_open) the hierarchy is the slab-distributed one: the 2D
  * and 3D built-in kinds the slabs run (NK_BRATU2D, every NK_HEAT2D_* and NK_HEAT3D_* kind), bc_zero!, y- / z-slabs.
@@ -317,7 +331,8 @@ int nk_mg_plan_slabs(const int64_t n_local[3], int32_t nranks, int32_t max_level
 int nk_mg_plan_semi(const int64_t n[3], const double h[3], const double k[3], double threshold, int32_t max_levels,
                     int64_t* extents, int32_t cap, int32_t* nlevels);
 /* nk_mg_create on caller-given level extents (extents[3 l + a], nlevels of them; opts->max_levels is ignored: the
- * list is the plan).  The same rejections as nk_mg_create; NK_E_ARG naming the reason when level 0 is not the
+ * list is the plan).  The same rejections as nk_mg_create, and periodic boundaries (NK_BC_PERIODIC has one plan,
+ * nk_mg_plan_periodic's); NK_E_ARG naming the reason when level 0 is not the
  * problem's grid, an axis of a level is neither kept nor n / 2 of an axis of more than 3 points, a level coarsens
  * no axis, or nlevels is not in 1 .. 32.  The transfers between two levels run the kernel instantiated for their set
  * of coarsened axes. */

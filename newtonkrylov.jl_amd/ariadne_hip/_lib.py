@@ -146,6 +146,7 @@ SIGNATURES = {
     "nk_mg_plan": (C.c_int, [C.POINTER(_I64), _I32, C.POINTER(_I64), _I32, C.POINTER(_I32)]),
     "nk_mg_create": (C.c_int, [_VP, _PP, C.POINTER(nk_mg_opts), C.POINTER(_VP)]),
     "nk_mg_plan_slabs": (C.c_int, [C.POINTER(_I64), _I32, _I32, C.POINTER(_I64), _I32, C.POINTER(_I32)]),
+    "nk_mg_plan_periodic": (C.c_int, [C.POINTER(_I64), _I32, C.POINTER(_I64), _I32, C.POINTER(_I32)]),
     "nk_mg_plan_semi": (C.c_int, [C.POINTER(_I64), _PD, _PD, _D, _I32, C.POINTER(_I64), _I32, C.POINTER(_I32)]),
     "nk_mg_create_levels": (C.c_int, [_VP, _PP, C.POINTER(nk_mg_opts), C.POINTER(_I64), _I32, C.POINTER(_VP)]),
     "nk_mg_level_extents": (C.c_int, [_VP, C.POINTER(_I64), _I32, C.POINTER(_I32)]),

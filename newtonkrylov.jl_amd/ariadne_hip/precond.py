@@ -155,7 +155,8 @@ class MultigridPreconditioner(Preconditioner):
     level, weight `omega`, default 2d / (2d + 1)), per axis n -> n // 2 while n > 3 (`max_levels` = 0: until
     every axis is <= 3), rediscretised coarse operators, linear prolongation, restriction D^-1 P^T.  A fixed
     linear map: valid as N or M of gmres as well as fgmres.  Built-in stencil residuals, bc_zero_, one
-    rank; everything else raises NotImplementedError.  `update(J)` refreshes s = λ exp(u) for a new u.
+    rank (`distributed=True`: slabs; `periodic=True`: bc_periodic_); everything else raises NotImplementedError.
+    `update(J)` refreshes s = λ exp(u) for a new u.
 
     `spd=True` (or `.spd = True` at any time) is the SPD form for CG's M: z = σ V(v) with σ the sign of the level-0
     diagonal (-1 for the built-in Jacobians, which are negative definite: M = -V, as the Jacobi M is
@@ -177,12 +178,21 @@ class MultigridPreconditioner(Preconditioner):
     level runs `coarse_sweeps` sweeps -- raise them on many ranks.  Construction, `update` and
     `set_coefficients` are collective, and every rank must apply the cycle; `levels` reports local extents.  2D and
     3D built-in kinds, bc_zero_, full coarsening, no 3D blocks.  Without the flag a distributed context or a slab
-    keeps raising NotImplementedError."""
+    keeps raising NotImplementedError.
+
+    `periodic=True`: the hierarchy of a periodic grid, for the heat residuals with bc_periodic_ on one rank.  The levels
+    are nested (coarse point j is fine point 2 j): an axis is halved while it is even and has at least 6 points
+    (`multigrid_plan(shape, periodic=True)`), so extents (3, 4 or 5) * 2^k are the intended ones -- an odd axis is never
+    coarsened, which is valid but weak.  Neighbours and transfers wrap, the coarse operators keep the period
+    (h_l = h_0 n_0 / n_l); smoother, cycle, sign check, `spd`, `update` and `set_coefficients` work as above.  The
+    nearly constant mode (eigenvalue s = -1 against a large diagonal) is left to the Krylov method.
+    Full coarsening, not distributed.  Without the flag a periodic problem keeps raising NotImplementedError."""
 
     def __init__(self, J, nu: int = 2, coarse_sweeps: int = 8, omega: float | None = None, max_levels: int = 0,
-                 spd: bool = False, coarsening: str = "full", threshold: float = 0.5, distributed: bool = False):
-        self.distributed = bool(distributed)
-        prob = _mg_problem(J, distributed, coarsening)
+                 spd: bool = False, coarsening: str = "full", threshold: float = 0.5, distributed: bool = False,
+                 periodic: bool = False):
+        self.distributed, self.periodic = bool(distributed), bool(periodic)
+        prob = _mg_problem(J, distributed, coarsening, periodic)
         # the built-in Jacobians have the same k on every axis: the plan depends on the spacings alone
         self._create(J.u.ctx, J.u.grid, prob, nu, coarse_sweeps, omega, max_levels, coarsening, threshold, None)
         self.spd = spd
@@ -211,19 +221,24 @@ class MultigridPreconditioner(Preconditioner):
     @classmethod
     def from_coefficients(cls, grid, k, s, *, h=None, ctx=None, nu: int = 2, coarse_sweeps: int = 8,
                           omega: float | None = None, max_levels: int = 0, spd: bool = False, coarsening: str = "full",
-                          threshold: float = 0.5, distributed: bool = False):
+                          threshold: float = 0.5, distributed: bool = False, periodic: bool = False):
         """The V-cycle for A = Σ_a k[a] δ²_a(h[a]) + diag(s) on `grid` with caller-supplied coefficients: k per
         axis, s a DeviceArray on the grid or a constant; h = the spacings (default 1 / (n + 1) per axis).  Such an
         object keeps the caller's operator: the Newton drivers do not refresh it from the Jacobian (so it also
         serves a UserResidual); call update(J) yourself to switch it to a built-in J's coefficients.
         coarsening="semi": the plan is made from this k and h (a later set_coefficients keeps it).
         distributed=True: `grid` is this rank's slab (ah.slab, equal slabs) and s its slab of the coefficient; the
-        default spacings are those of the global grid."""
+        default spacings are those of the global grid.
+        periodic=True: the operator on the periodic grid (2D / 3D; neighbours wrap), default spacings 1 / n per axis."""
         from .device import default_context
 
         _mg_coarsening(coarsening, threshold)
+        if periodic:
+            _mg_periodic_check(distributed, coarsening)
+            if grid.dim == 1:
+                raise NotImplementedError("multigrid: periodic=True covers 2D and 3D grids (there is no periodic 1D kind)")
         self = cls.__new__(cls)
-        self.distributed = bool(distributed)
+        self.distributed, self.periodic = bool(distributed), bool(periodic)
         ctx = ctx or (s.ctx if isinstance(s, DeviceArray) else default_context())
         if distributed:
             _mg_slab_check(ctx, grid, coarsening)
@@ -232,13 +247,15 @@ class MultigridPreconditioner(Preconditioner):
         k = [float(x) for x in (k if hasattr(k, "__len__") else [k] * grid.dim)]
         if len(k) != grid.dim:
             raise ValueError("k: one coefficient per axis")
-        h = [float(x) for x in (h if h is not None else [1.0 / (n + 1) for n in grid.global_xyz])]
+        h = [float(x) for x in (h if h is not None else [1.0 / (n if periodic else n + 1) for n in grid.global_xyz])]
         if len(h) != grid.dim:
             raise ValueError("h: one spacing per axis")
         if isinstance(s, DeviceArray) and s.grid != grid:
             raise ValueError("s must be a DeviceArray on `grid` (or a constant)")
         prob = grid.geometry_problem()
         prob.hx, prob.hy, prob.hz = (h + [1.0, 1.0])[:3]
+        if periodic:  # the carrier kind: a heat kind of the grid's dimension, which bc_periodic_ is defined for
+            prob.kind, prob.bc = (_lib.NK_HEAT2D_EULER if grid.dim == 2 else _lib.NK_HEAT3D_EULER), _lib.NK_BC_PERIODIC
         self._create(ctx, grid, prob, nu, coarse_sweeps, omega, max_levels, coarsening, threshold, k)
         self.spd = spd
         return self.set_coefficients(k, s)
@@ -264,7 +281,7 @@ class MultigridPreconditioner(Preconditioner):
         """k and s of J(u) at J's current u (nk_mg_set_jacobian): call after u changed."""
         import ctypes as C
 
-        prob = _mg_problem(J, getattr(self, "distributed", False))
+        prob = _mg_problem(J, getattr(self, "distributed", False), periodic=getattr(self, "periodic", False))
         self.caller_operator = False
         if J.u.grid != self.grid or J.u.ctx is not self.ctx:
             raise ValueError("multigrid: J lives on another grid / context than the hierarchy")
@@ -347,7 +364,15 @@ def _mg_slab_check(ctx, grid, coarsening="full"):
         raise NotImplementedError("multigrid: slabs of an odd number of planes cannot be coarsened")
 
 
-def _mg_problem(J, distributed=False, coarsening="full"):
+def _mg_periodic_check(distributed, coarsening):
+    """periodic=True: what it does not combine with (NotImplementedError, on the host)"""
+    if distributed:
+        raise NotImplementedError("multigrid: periodic=True is not implemented with distributed=True")
+    if coarsening != "full":
+        raise NotImplementedError('multigrid: coarsening="semi" is not implemented with periodic=True')
+
+
+def _mg_problem(J, distributed=False, coarsening="full", periodic=False):
     """J's nk_problem if the multigrid preconditioner covers it; NotImplementedError naming the reason if not
     (checked on the host, before anything touches the device)."""
     from .problems import UserResidual
@@ -356,13 +381,19 @@ def _mg_problem(J, distributed=False, coarsening="full"):
         raise NotImplementedError("multigrid: a user residual has no known stencil coefficients -- build the V-cycle "
                                   "with MultigridPreconditioner.from_coefficients(grid, k, s)")
     ctx, grid = J.u.ctx, J.u.grid
+    if periodic:
+        _mg_periodic_check(distributed, coarsening)
     if distributed:
         _mg_slab_check(ctx, grid, coarsening)
     elif getattr(ctx, "nranks", 1) != 1 or tuple(grid.shape_xyz) != tuple(grid.global_xyz):
         raise NotImplementedError("multigrid: one rank only (a distributed context / slab needs distributed=True)")
     prob = J.problem()
-    if prob.bc != _lib.NK_BC_ZERO:
-        raise NotImplementedError("multigrid: bc_zero_ only (periodic boundaries are not implemented)")
+    if periodic:
+        if prob.bc != _lib.NK_BC_PERIODIC:
+            raise ValueError("multigrid: periodic=True on a bc_zero_ problem (leave the keyword out)")
+    elif prob.bc != _lib.NK_BC_ZERO:
+        raise NotImplementedError("multigrid: a periodic problem (bc_periodic_) needs the keyword periodic=True; "
+                                  "the default hierarchy is bc_zero_ only")
     if distributed and prob.kind == _lib.NK_BRATU3D:
         raise NotImplementedError("multigrid: 3D Bratu runs on one rank (distributed=True is not implemented for it)")
     return prob
@@ -379,12 +410,14 @@ def _mg_coarsening(coarsening, threshold):
 
 
 def multigrid_plan(shape_xyz, max_levels: int = 0, *, coarsening: str = "full", h=None, k=None, threshold: float = 0.5,
-                   nranks: int = 1) -> list:
+                   nranks: int = 1, periodic: bool = False) -> list:
     """The level extents of a grid (host only, no GPU): [(nx[, ny[, nz]]), ...].  coarsening="full": nk_mg_plan.
     "semi": nk_mg_plan_semi with the spacings h (default 1 / (n + 1) per axis), the coefficients k per axis
     (default all ones) and the threshold (MultigridPreconditioner).  nranks > 1: the plan of the slab-distributed
     hierarchy (distributed=True; nk_mg_plan_slabs) -- shape_xyz is one rank's LOCAL extents (equal slabs), and so
-    are the levels; NotImplementedError where no such hierarchy exists (an odd local slab extent, a 1D grid)."""
+    are the levels; NotImplementedError where no such hierarchy exists (an odd local slab extent, a 1D grid).
+    periodic=True: the plan of a periodic grid (nk_mg_plan_periodic): an axis is halved while it is even and has at
+    least 6 points; ValueError where a used axis has fewer than 3 points."""
     import ctypes as C
 
     coarsening, threshold = _mg_coarsening(coarsening, threshold)
@@ -392,6 +425,12 @@ def multigrid_plan(shape_xyz, max_levels: int = 0, *, coarsening: str = "full", 
     n = (C.c_int64 * 3)(*(list(shape_xyz) + [1, 1])[:3])
     ext = (C.c_int64 * (3 * 64))()
     nl = C.c_int32(0)
+    if periodic:
+        _mg_periodic_check(int(nranks) != 1, coarsening)
+        if load().nk_mg_plan_periodic(n, int(max_levels), ext, 64, C.byref(nl)) != 0:
+            raise ValueError(f"multigrid: no periodic plan for {tuple(shape_xyz)} (every used axis needs at least 3 points, "
+                             "max_levels >= 0)")
+        return [tuple(int(ext[3 * l + a]) for a in range(dim)) for l in range(min(nl.value, 64))]
     if int(nranks) != 1:
         if coarsening != "full":
             raise NotImplementedError('multigrid: coarsening="semi" is not implemented on slabs (nranks > 1)')
@@ -420,8 +459,9 @@ class _MultigridFactory:
         self.opts, self.key, self.mg = dict(opts), None, None
 
     def __call__(self, J):
-        prob = _mg_problem(J, self.opts.get("distributed", False), self.opts.get("coarsening", "full"))
-        key = (id(J.u.ctx), J.u.grid, prob.kind, prob.hx, prob.hy, prob.hz)  # (the options are the factory's own)
+        prob = _mg_problem(J, self.opts.get("distributed", False), self.opts.get("coarsening", "full"),
+                           self.opts.get("periodic", False))
+        key = (id(J.u.ctx), J.u.grid, prob.kind, prob.hx, prob.hy, prob.hz, prob.bc)  # (the options are the factory's own)
         if self.mg is None or self.key != key or self.mg.handle is None or self.mg.ctx is not J.u.ctx:
             self.free()
             self.key, self.mg = key, MultigridPreconditioner(J, **self.opts)
@@ -442,7 +482,8 @@ def multigrid(J=None, **opts):
     keeps nothing beyond the solve.  Called with an operator, `multigrid(J)` is MultigridPreconditioner(J).
     `M=multigrid(spd=True)` is the SPD form, CG's and MINRES's preconditioner (algo="cg" / "minres"); `N=multigrid(coarsening="semi")` the
     semicoarsened hierarchy for grids whose spacings differ between the axes (MultigridPreconditioner);
-    `N=multigrid(distributed=True)` the hierarchy on equal slabs of a distributed context (every rank builds one)."""
+    `N=multigrid(distributed=True)` the hierarchy on equal slabs of a distributed context (every rank builds one);
+    `N=multigrid(periodic=True)` the hierarchy of a periodic grid (heat residuals with bc_periodic_)."""
     if J is None:
         _mg_coarsening(opts.get("coarsening", "full"), opts.get("threshold", 0.5))
         return _MultigridFactory(opts)

@@ -11,7 +11,10 @@
 // distributed context the hierarchy lives on equal slabs of the slowest axis: mg_plan_slabs cuts mg_plan's levels where
 // the local slab extent stops being even, the level arrays carry one ghost plane per side, and the same kernels run in
 // their slab instantiation (AX = the slab axis; 0: one rank) with the context's ghost-plane exchange between them --
-// the one-rank cycle of the global grid, bit for bit.  One text per expression: the device functions and the per-level
+// the one-rank cycle of the global grid, bit for bit.  A periodic grid (NK_BC_PERIODIC, the heat kinds, one rank) has a
+// hierarchy of its own: nested levels (mg_plan_per: an axis is halved while it is even and >= 6), neighbours that wrap
+// (the PER instantiations of the device functions, the per-level kernels and the tail) and transfers with fixed
+// footprints (k_mg_restrict_p / k_mg_prolong_p).  One text per expression: the device functions and the per-level
 // kernels are templates on AX, and mg_pick turns the runtime AX, RED, MASK, S32 and OUT into the instantiation a
 // launcher runs.  The host-only rules (plans, level-list validation, kernel choice, grids, the tail's extent, the
 // transfers' integer weights) are nk_mg_plan.hpp, which a CPU test calls.  DESIGN.md §10.
@@ -45,10 +48,26 @@ struct MgSl {
 };
 
 // Σ_a c_a (x_- + x_+) at point i, zero Dirichlet boundary.  Along AX the neighbours are the ghost planes, read as they
-// are (the local extent along AX may be 1); a y-slab grid is 2D
-template <int AX = 0>
+// are (the local extent along AX may be 1); a y-slab grid is 2D.  PER (one rank, AX = 0): a periodic grid -- the
+// neighbours wrap (point 0's lower neighbour is point n_a - 1), the same sums in the same order
+template <int AX = 0, bool PER = false>
 __device__ __forceinline__ double mg_off(const MgLv& L, const double* x, int i) {
     const int ix = i % L.nx, t = i / L.nx, iy = t % L.ny, iz = t / L.ny;
+    if constexpr (PER) {
+        const double xm = x[ix > 0 ? i - 1 : i + (L.nx - 1)], xp = x[ix + 1 < L.nx ? i + 1 : i - (L.nx - 1)];
+        double o = L.cx * (xm + xp);
+        if (L.ny > 1) {
+            const int wy = L.nx * (L.ny - 1);
+            const double ym = x[iy > 0 ? i - L.nx : i + wy], yp = x[iy + 1 < L.ny ? i + L.nx : i - wy];
+            o = o + L.cy * (ym + yp);
+        }
+        if (L.nz > 1) {
+            const int pl = L.nx * L.ny, wz = pl * (L.nz - 1);
+            const double zm = x[iz > 0 ? i - pl : i + wz], zp = x[iz + 1 < L.nz ? i + pl : i - wz];
+            o = o + L.cz * (zm + zp);
+        }
+        return o;
+    }
     const double xm = ix > 0 ? x[i - 1] : 0.0, xp = ix + 1 < L.nx ? x[i + 1] : 0.0;
     double o = L.cx * (xm + xp);
     if (AX == 1 || L.ny > 1) {
@@ -67,15 +86,15 @@ __device__ __forceinline__ double mg_off(const MgLv& L, const double* x, int i) 
 __device__ __forceinline__ double mg_sweep0_pt(double omega, const double* b, const double* idg, int i) {
     return omega * (idg[i] * b[i]);
 }
-template <int AX = 0>
+template <int AX = 0, bool PER = false>
 __device__ __forceinline__ double mg_sweep_pt(const MgLv& L, double omega, double om1, const double* x, const double* b,
                                               const double* idg, int i) {
-    const double t = b[i] - mg_off<AX>(L, x, i);
+    const double t = b[i] - mg_off<AX, PER>(L, x, i);
     return om1 * x[i] + omega * (idg[i] * t);
 }
-template <int AX = 0>
+template <int AX = 0, bool PER = false>
 __device__ __forceinline__ double mg_resid_pt(const MgLv& L, const double* x, const double* b, const double* dg, int i) {
-    return b[i] - (mg_off<AX>(L, x, i) + dg[i] * x[i]);
+    return b[i] - (mg_off<AX, PER>(L, x, i) + dg[i] * x[i]);
 }
 
 // the transfers' weights along one axis: mg_rax_t / mg_pax_t of nk_mg_plan.hpp, here with 64-bit products
@@ -150,16 +169,61 @@ __device__ __forceinline__ double mg_prolong_pt(const MgLv& Lf, const MgLv& Lc, 
                                 AX == 2 ? Lc.nz + 1 : Lc.nz);
 }
 
+// The periodic transfers (nested levels; mg_per_rax / mg_per_pax of nk_mg_plan.hpp give the wrapped indices).  cx, cy,
+// cz: the axis is coarsened -- compile-time constants in the row-shaped kernels, level data in the tail.  nxf / plf and
+// nxc / plc: a row and an xy plane of the source level.
+// R: per coarsened axis (r_m + r_p) + 2 r_c, the x axis innermost, then one division by D = 4 per coarsened axis (a
+// power of two).  A fixed order, and a constant r comes back exactly: (s + s) + 2 s = 4 s
+__device__ __forceinline__ double mg_restrict_per(int nxf, int plf, bool cx, bool cy, bool cz, const MgPerR& ax, const MgPerR& ay,
+                                                  const MgPerR& az, const double* r) {
+    auto line = [&](int base) { return cx ? fma(2.0, r[base + ax.c], r[base + ax.m] + r[base + ax.p]) : r[base + ax.c]; };
+    auto plane = [&](int base) {
+        return cy ? fma(2.0, line(base + ay.c * nxf), line(base + ay.m * nxf) + line(base + ay.p * nxf)) : line(base + ay.c * nxf);
+    };
+    const double v = cz ? fma(2.0, plane(az.c * plf), plane(az.m * plf) + plane(az.p * plf)) : plane(az.c * plf);
+    return v / ((cx ? 4.0 : 1.0) * (cy ? 4.0 : 1.0) * (cz ? 4.0 : 1.0));
+}
+// P: per coarsened axis e[j0] at an even fine index, (1 - w) e[j0] + w e[j1] (w = 1/2) at an odd one
+__device__ __forceinline__ double mg_prolong_per(int nxc, int plc, bool cx, bool cy, bool cz, const MgPerP& px, const MgPerP& py,
+                                                 const MgPerP& pz, const double* e) {
+    auto line = [&](int base) {
+        double v = e[base + px.j0];
+        if (cx && px.w != 0.0) v = (1.0 - px.w) * v + px.w * e[base + px.j1];
+        return v;
+    };
+    auto plane = [&](int base) {
+        double v = line(base + py.j0 * nxc);
+        if (cy && py.w != 0.0) v = (1.0 - py.w) * v + py.w * line(base + py.j1 * nxc);
+        return v;
+    };
+    double v = plane(pz.j0 * plc);
+    if (cz && pz.w != 0.0) v = (1.0 - pz.w) * v + pz.w * plane(pz.j1 * plc);
+    return v;
+}
+// one point of either, for the tail
+__device__ __forceinline__ double mg_restrict_per_pt(const MgLv& Lf, const MgLv& Lc, const double* r, int j) {
+    const int jx = j % Lc.nx, t = j / Lc.nx, jy = t % Lc.ny, jz = t / Lc.ny;
+    const bool cx = Lf.nx != Lc.nx, cy = Lf.ny != Lc.ny, cz = Lf.nz != Lc.nz;
+    return mg_restrict_per(Lf.nx, Lf.nx * Lf.ny, cx, cy, cz, cx ? mg_per_rax(Lf.nx, jx) : mg_per_rkeep(jx),
+                           cy ? mg_per_rax(Lf.ny, jy) : mg_per_rkeep(jy), cz ? mg_per_rax(Lf.nz, jz) : mg_per_rkeep(jz), r);
+}
+__device__ __forceinline__ double mg_prolong_per_pt(const MgLv& Lf, const MgLv& Lc, const double* e, int i) {
+    const int ix = i % Lf.nx, t = i / Lf.nx, iy = t % Lf.ny, iz = t / Lf.ny;
+    const bool cx = Lf.nx != Lc.nx, cy = Lf.ny != Lc.ny, cz = Lf.nz != Lc.nz;
+    return mg_prolong_per(Lc.nx, Lc.nx * Lc.ny, cx, cy, cz, cx ? mg_per_pax(Lc.nx, ix) : mg_per_pkeep(ix),
+                          cy ? mg_per_pax(Lc.ny, iy) : mg_per_pkeep(iy), cz ? mg_per_pax(Lc.nz, iz) : mg_per_pkeep(iz), e);
+}
+
 // ------------------------------------------------------------------------------ per-level kernels (AX: one rank or slabs)
 __global__ __launch_bounds__(kBlock) void k_mg_sweep0(int n, double omega, double* x, const double* b,
                                                      const double* __restrict__ idg) {
     NK_CHUNKED(i, n) x[i] = mg_sweep0_pt(omega, b, idg, (int)i);
 }
 // xn must not alias x (the ping-pong pair); b is only read at the point written
-template <int AX>
+template <int AX, bool PER>
 __global__ __launch_bounds__(kBlock) void k_mg_sweep(MgLv L, double omega, double om1, double* xn, const double* __restrict__ x,
                                                     const double* b, const double* __restrict__ idg) {
-    NK_CHUNKED(i, L.n) xn[i] = mg_sweep_pt<AX>(L, omega, om1, x, b, idg, (int)i);
+    NK_CHUNKED(i, L.n) xn[i] = mg_sweep_pt<AX, PER>(L, omega, om1, x, b, idg, (int)i);
 }
 // The sweep that writes the cycle's result z: the same per-point arithmetic times sigma (+-1: exact), and with RED the
 // partials of <b, z> (b = the cycle's input v, read at the point written anyway) in a fixed order, no atomics
@@ -176,7 +240,7 @@ __global__ __launch_bounds__(kBlock) void k_mg_sweep0_z(int n, double omega, dou
     }
     if (RED) publish(acc, part, fin, sh);
 }
-template <int AX, bool RED>
+template <int AX, bool PER, bool RED>
 __global__ __launch_bounds__(kBlock) void k_mg_sweep_z(MgLv L, double omega, double om1, double sigma, double* z,
                                                       const double* __restrict__ x, const double* b, const double* __restrict__ idg,
                                                       double* __restrict__ part, int fin) {
@@ -184,16 +248,16 @@ __global__ __launch_bounds__(kBlock) void k_mg_sweep_z(MgLv L, double omega, dou
     double acc = 0.0;
     NK_CHUNKED(i, L.n) {
         const double bi = b[i];
-        const double zi = sigma * mg_sweep_pt<AX>(L, omega, om1, x, b, idg, (int)i);
+        const double zi = sigma * mg_sweep_pt<AX, PER>(L, omega, om1, x, b, idg, (int)i);
         z[i] = zi;
         if (RED) acc = fma(bi, zi, acc);
     }
     if (RED) publish(acc, part, fin, sh);
 }
-template <int AX>
+template <int AX, bool PER>
 __global__ __launch_bounds__(kBlock) void k_mg_resid(MgLv L, double* __restrict__ r, const double* __restrict__ x,
                                                     const double* __restrict__ b, const double* __restrict__ dg) {
-    NK_CHUNKED(i, L.n) r[i] = mg_resid_pt<AX>(L, x, b, dg, (int)i);
+    NK_CHUNKED(i, L.n) r[i] = mg_resid_pt<AX, PER>(L, x, b, dg, (int)i);
 }
 // (S is read by the slab forms only)
 template <int AX>
@@ -242,6 +306,57 @@ __global__ __launch_bounds__(kBlock) void k_mg_prolong_m(MgLv Lf, MgLv Lc, int l
         const MgPx pz = (MASK & 4) ? mg_pax_t<I>(Lf.nz, Lc.nz, iz) : MgPx{iz + 1, 0.0};
         const int64_t i = row * Lf.nx + ix;
         x[i] = x[i] + mg_prolong_ax<MASK>(Lc, px, py, pz, e);
+    }
+}
+// The transfers of a periodic hierarchy, instantiated on the set MASK of coarsened axes (any non-empty set: an axis
+// that is odd or too short is kept while the others are halved).  Row-shaped on mg_rows' grid like the _m kernels: a
+// thread keeps its x index (its wrapped x indices are computed once), a wave reads and writes whole contiguous row
+// segments, kept axes cost no index arithmetic.  The levels are nested, so the footprints are fixed (3 / 2 points per
+// coarsened axis) and all indices are 32-bit (a level has fewer than 2^31 points); wraps are compare-and-select.  The
+// row's (y, z) is divided out once per thread and then stepped: no integer division per point.
+struct MgRowIt {
+    int row, y, z, step, sy, sz;
+};
+__device__ __forceinline__ MgRowIt mg_row_first(int ny, int lbx) {
+    const int rpb = kBlock >> lbx, row = (int)blockIdx.y * rpb + (int)(threadIdx.x >> lbx), step = (int)gridDim.y * rpb;
+    return MgRowIt{row, row % ny, row / ny, step, step % ny, step / ny};
+}
+__device__ __forceinline__ void mg_row_next(MgRowIt& it, int ny) {
+    it.row += it.step;
+    it.y += it.sy;
+    it.z += it.sz;
+    if (it.y >= ny) {
+        it.y -= ny;
+        ++it.z;
+    }
+}
+template <int MASK>
+__global__ __launch_bounds__(kBlock) void k_mg_restrict_p(MgLv Lf, MgLv Lc, int lbx, double* __restrict__ bc,
+                                                         const double* __restrict__ r) {
+    constexpr bool CX = (MASK & 1) != 0, CY = (MASK & 2) != 0, CZ = (MASK & 4) != 0;
+    const int jx = (int)(blockIdx.x << lbx) + (int)(threadIdx.x & ((1u << lbx) - 1));
+    if (jx >= Lc.nx) return;
+    const MgPerR ax = CX ? mg_per_rax(Lf.nx, jx) : mg_per_rkeep(jx);
+    const int rows = Lc.ny * Lc.nz, plf = Lf.nx * Lf.ny;
+    for (MgRowIt it = mg_row_first(Lc.ny, lbx); it.row < rows; mg_row_next(it, Lc.ny)) {
+        const MgPerR ay = CY ? mg_per_rax(Lf.ny, it.y) : mg_per_rkeep(it.y);
+        const MgPerR az = CZ ? mg_per_rax(Lf.nz, it.z) : mg_per_rkeep(it.z);
+        bc[it.row * Lc.nx + jx] = mg_restrict_per(Lf.nx, plf, CX, CY, CZ, ax, ay, az, r);
+    }
+}
+template <int MASK>
+__global__ __launch_bounds__(kBlock) void k_mg_prolong_p(MgLv Lf, MgLv Lc, int lbx, double* __restrict__ x,
+                                                        const double* __restrict__ e) {
+    constexpr bool CX = (MASK & 1) != 0, CY = (MASK & 2) != 0, CZ = (MASK & 4) != 0;
+    const int ix = (int)(blockIdx.x << lbx) + (int)(threadIdx.x & ((1u << lbx) - 1));
+    if (ix >= Lf.nx) return;
+    const MgPerP px = CX ? mg_per_pax(Lc.nx, ix) : mg_per_pkeep(ix);
+    const int rows = Lf.ny * Lf.nz, plc = Lc.nx * Lc.ny;
+    for (MgRowIt it = mg_row_first(Lf.ny, lbx); it.row < rows; mg_row_next(it, Lf.ny)) {
+        const MgPerP py = CY ? mg_per_pax(Lc.ny, it.y) : mg_per_pkeep(it.y);
+        const MgPerP pz = CZ ? mg_per_pax(Lc.nz, it.z) : mg_per_pkeep(it.z);
+        const int i = it.row * Lf.nx + ix;
+        x[i] = x[i] + mg_prolong_per(Lc.nx, plc, CX, CY, CZ, px, py, pz, e);
     }
 }
 // set-up: diag = dsum + s (dsum = Σ_a -2 c_a, summed in axis order on the host) and 1 / diag
@@ -306,6 +421,7 @@ struct MgTail {
     double* x;        // its result
 };
 
+template <bool PER>
 __device__ __forceinline__ void mg_tail_sweeps(const MgLv& L, double omega, double om1, double* xa, double* xb, const double* b,
                                                const double* idg, int done, int sweeps) {
     for (int s = 0; s < sweeps; ++s, ++done) {
@@ -314,15 +430,16 @@ __device__ __forceinline__ void mg_tail_sweeps(const MgLv& L, double omega, doub
         } else {
             const double* x = (done & 1) ? xa : xb;
             double* xn = (done & 1) ? xb : xa;
-            for (int i = threadIdx.x; i < L.n; i += kMgTailThreads) xn[i] = mg_sweep_pt(L, omega, om1, x, b, idg, i);
+            for (int i = threadIdx.x; i < L.n; i += kMgTailThreads) xn[i] = mg_sweep_pt<0, PER>(L, omega, om1, x, b, idg, i);
         }
         __syncthreads();
     }
 }
 
 // OUT = 0: the cycle as it is.  OUT = 1: level 0 is the tail's first level and the closing loop writes sigma x.
-// OUT = 2: that, and <b, z> from the LDS copy of b into the one partial part[0].
-template <int OUT>
+// OUT = 2: that, and <b, z> from the LDS copy of b into the one partial part[0].  PER: a periodic hierarchy, from the
+// same device functions on the LDS pointers.
+template <int OUT, bool PER>
 __global__ __launch_bounds__(kMgTailThreads) void k_mg_tail(MgTail T, double sigma, double* part, int fin) {
     extern __shared__ double mg_lds[];
 #define MG_XA(l) (mg_lds + T.off[l])
@@ -341,14 +458,14 @@ __global__ __launch_bounds__(kMgTailThreads) void k_mg_tail(MgTail T, double sig
     for (int l = 0; l < T.nlev; ++l) {
         const MgLv& L = T.lv[l];
         const bool last = l == T.nlev - 1;
-        mg_tail_sweeps(L, T.omega, T.om1, MG_XA(l), MG_XB(l), MG_B(l), MG_IDG(l), 0, last ? T.cs : T.nu);
+        mg_tail_sweeps<PER>(L, T.omega, T.om1, MG_XA(l), MG_XB(l), MG_B(l), MG_IDG(l), 0, last ? T.cs : T.nu);
         if (last) break;
         const double* x = (T.nu & 1) ? MG_XA(l) : MG_XB(l);
         double* r = (T.nu & 1) ? MG_XB(l) : MG_XA(l);
-        for (int i = threadIdx.x; i < L.n; i += kMgTailThreads) r[i] = mg_resid_pt(L, x, MG_B(l), MG_DG(l), i);
+        for (int i = threadIdx.x; i < L.n; i += kMgTailThreads) r[i] = mg_resid_pt<0, PER>(L, x, MG_B(l), MG_DG(l), i);
         __syncthreads();
         const MgLv& Lc = T.lv[l + 1];
-        for (int j = threadIdx.x; j < Lc.n; j += kMgTailThreads) MG_B(l + 1)[j] = mg_restrict_pt(L, Lc, r, j);
+        for (int j = threadIdx.x; j < Lc.n; j += kMgTailThreads) MG_B(l + 1)[j] = PER ? mg_restrict_per_pt(L, Lc, r, j) : mg_restrict_pt(L, Lc, r, j);
         __syncthreads();
     }
     // ascent
@@ -358,9 +475,9 @@ __global__ __launch_bounds__(kMgTailThreads) void k_mg_tail(MgTail T, double sig
         const int kc = (l + 1 == T.nlev - 1) ? T.cs : 2 * T.nu;  // sweeps level l + 1 has seen
         const double* e = (kc & 1) ? MG_XA(l + 1) : MG_XB(l + 1);
         double* x = (T.nu & 1) ? MG_XA(l) : MG_XB(l);
-        for (int i = threadIdx.x; i < L.n; i += kMgTailThreads) x[i] = x[i] + mg_prolong_pt(L, Lc, e, i);
+        for (int i = threadIdx.x; i < L.n; i += kMgTailThreads) x[i] = x[i] + (PER ? mg_prolong_per_pt(L, Lc, e, i) : mg_prolong_pt(L, Lc, e, i));
         __syncthreads();
-        mg_tail_sweeps(L, T.omega, T.om1, MG_XA(l), MG_XB(l), MG_B(l), MG_IDG(l), T.nu, T.nu);
+        mg_tail_sweeps<PER>(L, T.omega, T.om1, MG_XA(l), MG_XB(l), MG_B(l), MG_IDG(l), T.nu, T.nu);
     }
     const int k0 = T.nlev == 1 ? T.cs : 2 * T.nu;
     const double* x0 = (k0 & 1) ? MG_XA(0) : MG_XB(0);
@@ -413,6 +530,8 @@ struct nk_mg {
     int slab_ax = 0;              // 0: one rank; 1 / 2: the slab axis (y of a 2D grid, z of a 3D grid)
     int ng[kMgMaxLevels] = {};    // global extent of the level along the slab axis (nranks x the local one)
     int64_t ghost[kMgMaxLevels] = {};  // doubles of the ghost plane before and after xa, xb, b, s (0: one rank)
+    // a periodic hierarchy (NK_BC_PERIODIC, one rank): nested levels of mg_plan_per, the PER kernels
+    bool per = false;
 };
 
 namespace {
@@ -446,10 +565,14 @@ int mg_launch_sweep(nk_mg* m, int l, double* xn, const double* x, const double* 
     const MgLv& L = m->lv[l];
     if (m->slab_ax) NK_TRY(mg_exchange(m, l, x));
     return launch(m->c, "mg_sweep", 32.0 * L.n, [&] {
-        mg_pick<int, 0, 1, 2>(m->slab_ax, [&](auto AX) {
-            hipLaunchKernelGGL(k_mg_sweep<AX.value>, dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, m->omega,
+        if (m->per)
+            hipLaunchKernelGGL((k_mg_sweep<0, true>), dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, m->omega,
                                1.0 - m->omega, xn, x, b, m->idg[l]);
-        });
+        else
+            mg_pick<int, 0, 1, 2>(m->slab_ax, [&](auto AX) {
+                hipLaunchKernelGGL((k_mg_sweep<AX.value, false>), dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, m->omega,
+                                   1.0 - m->omega, xn, x, b, m->idg[l]);
+            });
     });
 }
 // the residual of level l's x into r (slabs: x's ghost planes first)
@@ -457,9 +580,13 @@ int mg_launch_resid(nk_mg* m, int l, double* r, const double* x, const double* b
     const MgLv& L = m->lv[l];
     if (m->slab_ax) NK_TRY(mg_exchange(m, l, x));
     return launch(m->c, "mg_resid", 32.0 * L.n, [&] {
-        mg_pick<int, 0, 1, 2>(m->slab_ax, [&](auto AX) {
-            hipLaunchKernelGGL(k_mg_resid<AX.value>, dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, r, x, b, m->dg[l]);
-        });
+        if (m->per)
+            hipLaunchKernelGGL((k_mg_resid<0, true>), dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, r, x, b, m->dg[l]);
+        else
+            mg_pick<int, 0, 1, 2>(m->slab_ax, [&](auto AX) {
+                hipLaunchKernelGGL((k_mg_resid<AX.value, false>), dim3(wide_blocks(L.n)), dim3(kBlock), 0, m->c->stream, L, r, x, b,
+                                   m->dg[l]);
+            });
     });
 }
 // how the cycle's last launch writes z: times sigma, with the partials of <v, z> into *red when given
@@ -484,9 +611,12 @@ int mg_launch_sweep_z(nk_mg* m, double* z, const double* x, const double* b, con
             if (!x)
                 hipLaunchKernelGGL(k_mg_sweep0_z<RED.value>, dim3(g), dim3(kBlock), 0, c->stream, L.n, m->omega, o.sigma, z, b,
                                    m->idg[0], part, fin);
+            else if (m->per)
+                hipLaunchKernelGGL((k_mg_sweep_z<0, true, RED.value>), dim3(g), dim3(kBlock), 0, c->stream, L, m->omega,
+                                   1.0 - m->omega, o.sigma, z, x, b, m->idg[0], part, fin);
             else
                 mg_pick<int, 0, 1, 2>(m->slab_ax, [&](auto AX) {
-                    hipLaunchKernelGGL((k_mg_sweep_z<AX.value, RED.value>), dim3(g), dim3(kBlock), 0, c->stream, L, m->omega,
+                    hipLaunchKernelGGL((k_mg_sweep_z<AX.value, false, RED.value>), dim3(g), dim3(kBlock), 0, c->stream, L, m->omega,
                                        1.0 - m->omega, o.sigma, z, x, b, m->idg[0], part, fin);
                 });
         });
@@ -528,8 +658,19 @@ const char* const kMgProlongName[7] = {"mg_prolong",   "mg_prolong_x",  "mg_prol
 
 // The transfers: the general kernel in its AX form (slabs: the source's ghost planes first), or the instantiation on
 // the mask of a semicoarsened level pair.  setup: the restriction of s during set-up (a profiler class of its own)
+// a periodic level pair: the set of coarsened axes (never empty: every level of mg_plan_per halves an axis)
+int mg_per_mask(const MgLv& Lf, const MgLv& Lc) { return (Lf.nx != Lc.nx ? 1 : 0) | (Lf.ny != Lc.ny ? 2 : 0) | (Lf.nz != Lc.nz ? 4 : 0); }
+
 int mg_restrict(nk_mg* m, int l, double* bc, const double* r, bool setup) {
     const MgLv &Lf = m->lv[l], &Lc = m->lv[l + 1];
+    if (m->per) {
+        const MgRows g = mg_rows(Lc.nx, (int64_t)Lc.ny * Lc.nz);
+        return launch(m->c, setup ? "mg_setup_restrict_per" : "mg_restrict_per", 8.0 * Lf.n + 8.0 * Lc.n, [&] {
+            mg_pick<int, 1, 2, 3, 4, 5, 6, 7>(mg_per_mask(Lf, Lc), [&](auto MASK) {
+                hipLaunchKernelGGL(k_mg_restrict_p<MASK.value>, dim3(g.gx, g.gy), dim3(kBlock), 0, m->c->stream, Lf, Lc, g.lbx, bc, r);
+            });
+        });
+    }
     if (m->slab_ax) NK_TRY(mg_exchange(m, l, r));
     const MgXfer t = mg_xfer(m, l);
     const MgSl S = mg_slab(m, l);
@@ -550,6 +691,14 @@ int mg_restrict(nk_mg* m, int l, double* bc, const double* r, bool setup) {
 }
 int mg_prolong(nk_mg* m, int l, double* x, const double* e) {
     const MgLv &Lf = m->lv[l], &Lc = m->lv[l + 1];
+    if (m->per) {
+        const MgRows g = mg_rows(Lf.nx, (int64_t)Lf.ny * Lf.nz);
+        return launch(m->c, "mg_prolong_per", 16.0 * Lf.n + 8.0 * Lc.n, [&] {
+            mg_pick<int, 1, 2, 3, 4, 5, 6, 7>(mg_per_mask(Lf, Lc), [&](auto MASK) {
+                hipLaunchKernelGGL(k_mg_prolong_p<MASK.value>, dim3(g.gx, g.gy), dim3(kBlock), 0, m->c->stream, Lf, Lc, g.lbx, x, e);
+            });
+        });
+    }
     if (m->slab_ax) NK_TRY(mg_exchange(m, l + 1, e));
     const MgXfer t = mg_xfer(m, l);
     const MgSl S = mg_slab(m, l);
@@ -616,7 +765,9 @@ int mg_setup(nk_mg* m, const double k[3], const nk_problem* jac, const double* u
         if (m->slab_ax) ext[m->slab_ax] = m->ng[l];  // the spacing of the global grid
         double cc[3] = {0.0, 0.0, 0.0}, dsum = 0.0;
         for (int a = 0; a < m->dim; ++a) {
-            const double h = l == 0 ? m->h0[a] : m->len[a] / (double)(ext[a] + 1);
+            // periodic: the period n_a^0 h_a^0 stays, so h_a^l = h_a^0 (n_a^0 / n_a^l), an exact power of two
+            const int n0a = a == 0 ? m->lv[0].nx : (a == 1 ? m->lv[0].ny : m->lv[0].nz);
+            const double h = l == 0 ? m->h0[a] : (m->per ? m->h0[a] * (double)(n0a / ext[a]) : m->len[a] / (double)(ext[a] + 1));
             cc[a] = k[a] / (h * h);
             dsum = a == 0 ? -2.0 * cc[a] : dsum + -2.0 * cc[a];
         }
@@ -693,6 +844,12 @@ int nk_mg_plan(const int64_t n[3], int32_t max_levels, int64_t* extents, int32_t
     return mg_plan_out(ext, mg_plan(n, max_levels, ext), extents, cap, nlevels);
 }
 
+int nk_mg_plan_periodic(const int64_t n[3], int32_t max_levels, int64_t* extents, int32_t cap, int32_t* nlevels) {
+    if (!mg_plan_args(n, max_levels, extents, cap, nlevels) || mg_plan_per_why(n, 0)) return NK_E_ARG;
+    int64_t ext[kMgMaxLevels][3];
+    return mg_plan_out(ext, mg_plan_per(n, max_levels, ext), extents, cap, nlevels);
+}
+
 int nk_mg_plan_slabs(const int64_t n_local[3], int32_t nranks, int32_t max_levels, int64_t* extents, int32_t cap,
                      int32_t* nlevels) {
     if (!mg_plan_args(n_local, max_levels, extents, cap, nlevels)) return NK_E_ARG;
@@ -728,7 +885,15 @@ int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int6
     if (!stencil_kind(p->kind))
         return fail(c, NK_E_ARG, "multigrid: built-in stencil kinds only (a user residual's coefficients are unknown; "
                                  "give them with nk_mg_set_operator on a built-in kind's grid)");
-    if (p->bc != NK_BC_ZERO) return fail(c, NK_E_ARG, "multigrid: bc_zero! only (periodic boundaries are not implemented)");
+    // periodic boundaries: the heat kinds on one rank, on mg_plan_per's nested levels
+    const bool per = p->bc == NK_BC_PERIODIC;
+    if (p->bc != NK_BC_ZERO && !per) return fail(c, NK_E_ARG, "multigrid: bc_zero! or bc_periodic! (unknown bc)");
+    if (per && !kind_of(p->kind).periodic)
+        return fail(c, NK_E_ARG, "multigrid: periodic boundaries are implemented for the heat kinds only (this kind is bc_zero! only)");
+    if (per && c->nranks != 1)
+        return fail(c, NK_E_ARG, "multigrid: periodic boundaries are not implemented on a distributed context");
+    if (per && given)
+        return fail(c, NK_E_ARG, "multigrid: periodic boundaries are not implemented with a level list (semicoarsening)");
     // a distributed context: equal slabs of the slowest axis.  Every refusal depends on values all
     // ranks hold alike (kind, bc, process grid, local extents -- equal by precondition -- and options), and comes
     // before the first exchange is enqueued
@@ -762,10 +927,14 @@ int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int6
         const char* why = nullptr;
         nlev = mg_plan_slabs(n0, c->nranks, opts ? opts->max_levels : 0, ext, &slab_ax, &why);
         if (nlev == 0) return fail(c, NK_E_ARG, std::string("multigrid on a distributed context: ") + why);
+    } else if (per) {
+        if (const char* why = mg_plan_per_why(n0, g.dim)) return fail(c, NK_E_ARG, std::string("multigrid on a periodic grid: ") + why);
+        nlev = mg_plan_per(n0, opts ? opts->max_levels : 0, ext);
     } else {
         nlev = mg_plan(n0, opts ? opts->max_levels : 0, ext);
     }
     nk_mg* m = new nk_mg();
+    m->per = per;
     m->c = c;
     m->prob = *p;
     m->dim = g.dim;
@@ -821,8 +990,9 @@ int mg_create(nk_ctx* c, const nk_problem* p, const nk_mg_opts* opts, const int6
     if (m->tail < m->nlev_alloc) {
         // the same limit for every hierarchy (a per-hierarchy value could lower it under an earlier, larger tail)
         hipError_t e = tail.lds <= kMgTailLds ? hipSuccess : hipErrorInvalidValue;
-        for (const void* f : {reinterpret_cast<const void*>(k_mg_tail<0>), reinterpret_cast<const void*>(k_mg_tail<1>),
-                              reinterpret_cast<const void*>(k_mg_tail<2>)})
+        for (const void* f : {reinterpret_cast<const void*>(k_mg_tail<0, false>), reinterpret_cast<const void*>(k_mg_tail<1, false>),
+                              reinterpret_cast<const void*>(k_mg_tail<2, false>), reinterpret_cast<const void*>(k_mg_tail<0, true>),
+                              reinterpret_cast<const void*>(k_mg_tail<1, true>), reinterpret_cast<const void*>(k_mg_tail<2, true>)})
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMgTailLds);
         if (e != hipSuccess) {
             mg_free(m);
@@ -897,8 +1067,8 @@ int nk_mg_set_jacobian(nk_mg* m, const nk_problem* p, const double* u) {
     if (!m || !p || !u) return NK_E_ARG;
     nk_ctx* c = m->c;
     if (p->kind != m->prob.kind || p->nx != m->prob.nx || p->ny != m->prob.ny || p->nz != m->prob.nz || p->hx != m->prob.hx ||
-        (m->dim >= 2 && p->hy != m->prob.hy) || (m->dim == 3 && p->hz != m->prob.hz) || p->bc != NK_BC_ZERO)
-        return fail(c, NK_E_ARG, "multigrid: the problem does not match the hierarchy's (kind, grid, spacings, bc_zero!)");
+        (m->dim >= 2 && p->hy != m->prob.hy) || (m->dim == 3 && p->hz != m->prob.hz) || p->bc != m->prob.bc)
+        return fail(c, NK_E_ARG, "multigrid: the problem does not match the hierarchy's (kind, grid, spacings, bc)");
     double k[3] = {0.0, 0.0, 0.0};
     const int64_t n = m->lv[0].n;
     if (kind_of(p->kind).ignition) {
@@ -991,8 +1161,10 @@ int nk::mg_apply_red(nk_mg* m, double* z, const double* v, Red* red) {
         double* part = mode == 2 ? red_out(c, 1, red, &fin) : nullptr;
         NK_TRY(launch(c, mode == 2 ? "mg_tail_dot" : "mg_tail", 16.0 * pts + 16.0 * m->lv[G].n, [&] {
             mg_pick<int, 0, 1, 2>(mode, [&](auto OUT) {
-                hipLaunchKernelGGL(k_mg_tail<OUT.value>, dim3(1), dim3(kMgTailThreads), lds, c->stream, T, mode ? out.sigma : 1.0,
-                                   part, fin);
+                mg_pick<bool, false, true>(m->per, [&](auto PER) {
+                    hipLaunchKernelGGL((k_mg_tail<OUT.value, PER.value>), dim3(1), dim3(kMgTailThreads), lds, c->stream, T,
+                                       mode ? out.sigma : 1.0, part, fin);
+                });
             });
         }));
     }

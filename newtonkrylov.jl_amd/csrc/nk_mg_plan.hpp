@@ -100,6 +100,33 @@ inline int mg_plan_slabs(const int64_t n0[3], int nranks, int max_levels, int64_
     return L;
 }
 
+// The plan of a periodic grid (neighbours wrap, n_a >= 3 per used axis).  The levels are nested -- coarse point j is
+// fine point 2 j -- so an axis can be halved only while it is even, and n_a / 2 >= 3 must remain: an axis is halvable
+// when n_a is even and n_a >= 6.  Level l + 1 halves every halvable axis and keeps the others; the plan ends when no
+// axis is halvable.  Extents (3, 4 or 5) 2^k coarsen all the way down; an odd axis is never coarsened.
+inline bool mg_per_halvable(int64_t n) { return n % 2 == 0 && n >= 6; }
+// null where a periodic hierarchy exists on the grid n0 of `dim` used axes (the first dim ones), else the reason.
+// dim = 0: taken from the extents -- the axes up to the last one of more than one point (a plan query has no kind)
+inline const char* mg_plan_per_why(const int64_t n0[3], int dim) {
+    if (dim == 0) dim = n0[2] > 1 ? 3 : (n0[1] > 1 ? 2 : 1);
+    for (int a = 0; a < 3; ++a)
+        if (a < dim ? n0[a] < 3 : n0[a] != 1) return "a periodic axis needs at least 3 points (and an unused one has 1)";
+    return nullptr;
+}
+inline int mg_plan_per(const int64_t n0[3], int max_levels, int64_t (*ext)[3]) {
+    int64_t n[3] = {n0[0], n0[1], n0[2]};
+    int L = 0;
+    for (;;) {
+        for (int a = 0; a < 3; ++a) ext[L][a] = n[a];
+        ++L;
+        if (L == kMgMaxLevels || (max_levels > 0 && L >= max_levels)) break;
+        if (!mg_per_halvable(n[0]) && !mg_per_halvable(n[1]) && !mg_per_halvable(n[2])) break;
+        for (int a = 0; a < 3; ++a)
+            if (mg_per_halvable(n[a])) n[a] /= 2;
+    }
+    return L;
+}
+
 // A caller's level list (nlevels x 3 extents) for the grid n0: null where it is a hierarchy -- level 0 is the grid,
 // every later level keeps each axis or halves one of more than 3 points, and coarsens at least one -- else the reason
 // (a literal, or written into buf where it names the level)
@@ -228,5 +255,32 @@ NK_MG_HD MgPx mg_pax_t(int nf, int nc, int i) {
     const I q = (I)(i + 1) * (nc + 1), F = nf + 1;  // q reaches n_f^2 / 2 (I as in mg_rax_t)
     return MgPx{(int)(q / F), (double)(q % F) / (double)F};
 }
+
+// ---------------------------------------------------------------- periodic transfers (nested levels, n_f = 2 n_c)
+// one coarsened axis of R = D^-1 P^T for coarse point j: the fine points m = (2 j - 1) mod n_f, c = 2 j and
+// p = (2 j + 1) mod n_f with the integer weights 1, 2, 1 (D = 4).  n_f is even, so only m wraps (at j = 0);
+// 32-bit indices, the wrap a compare-and-select
+struct MgPerR {
+    int m, c, p;
+};
+NK_MG_HD MgPerR mg_per_rax(int nf, int j) {
+    const int c = 2 * j;
+    return MgPerR{j > 0 ? c - 1 : nf - 1, c, c + 1};
+}
+// an axis that was kept: the identity -- mg_restrict_per reads c alone there and divides by 1 (m and p only keep the
+// type of the three axes the same)
+NK_MG_HD MgPerR mg_per_rkeep(int j) { return MgPerR{j, j, j}; }
+
+// one coarsened axis of P for fine point i: e_f[i] = (1 - w) e_c[j0] + w e_c[j1]; an even i takes e_c[i / 2] (w = 0,
+// j1 is not read), an odd one w = 1/2 between j0 = (i - 1) / 2 and j1 = ((i + 1) / 2) mod n_c
+struct MgPerP {
+    int j0, j1;
+    double w;
+};
+NK_MG_HD MgPerP mg_per_pax(int nc, int i) {
+    const int j0 = i >> 1, j1 = j0 + 1 < nc ? j0 + 1 : 0;
+    return (i & 1) ? MgPerP{j0, j1, 0.5} : MgPerP{j0, j0, 0.0};
+}
+NK_MG_HD MgPerP mg_per_pkeep(int i) { return MgPerP{i, i, 0.0}; }
 
 }  // namespace nk

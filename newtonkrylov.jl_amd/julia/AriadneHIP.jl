@@ -461,8 +461,10 @@ nkprecond(P::HipGmresPreconditioner) = NkPrecond(NK_PRECOND_GMRES, C_NULL, C_NUL
 
 # Geometric multigrid V-cycle for the stencil Jacobians (NK_PRECOND_MG, nkhip.h): built-in residuals,
 # bc_zero!, one rank (on a distributed context nk_mg_create builds the slab-distributed hierarchy: equal slabs, see
-# nkhip.h and mg_plan_slabs).  `N = hip_multigrid` is a factory: one hierarchy per (context, grid, kind), refreshed
-# from each Newton step's u (nk_mg_set_jacobian).  Valid for :gmres and :fgmres, as N or M; and in its SPD form
+# nkhip.h and mg_plan_slabs).  A heat problem with NK_BC_PERIODIC on one rank gets the periodic hierarchy -- nested
+# levels, wrapped neighbours and transfers, see nkhip.h and mg_plan_periodic -- without a keyword: this shim hands the
+# problem's bc to nk_mg_create as it is (Python asks for periodic=True).  `N = hip_multigrid` is a factory: one
+# hierarchy per (context, grid, kind, spacings, bc), refreshed from each Newton step's u (nk_mg_set_jacobian).  Valid for :gmres and :fgmres, as N or M; and in its SPD form
 # (`spd = true` / mg_set_spd!: z = σ V(v), σ the sign of the level-0 diagonal) as M of :cg -- `M = hip_multigrid_spd`.
 const NK_PRECOND_MG = Int32(5)
 struct NkMgOpts
@@ -559,6 +561,17 @@ function mg_plan_slabs(n::NTuple{3, Int64}, nranks::Integer; max_levels = 0)
     rc == 0 || error("nk_mg_plan_slabs: no slab plan (a 1D grid, an odd local slab extent, fewer than 2 ranks)")
     return [Tuple(ext[3l + 1:3l + 3]) for l in 0:nl[] - 1]
 end
+# the plan of a periodic grid (host only): an axis is halved while it is even and has at least 6 points (the levels are
+# nested, and at least 3 points remain); extents (3, 4 or 5) 2^k coarsen all the way.  HipMultigridPreconditioner builds
+# that hierarchy for a heat problem with NK_BC_PERIODIC (nk_mg_create, nkhip.h)
+function mg_plan_periodic(n::NTuple{3, Int64}; max_levels = 0)
+    ext = Vector{Int64}(undef, 3 * 64)
+    nl = Ref{Int32}(0)
+    rc = ccall((:nk_mg_plan_periodic, libnkhip), Cint, (Ref{NTuple{3, Int64}}, Int32, Ptr{Int64}, Int32, Ref{Int32}),
+               Ref(n), max_levels, ext, 64, nl)
+    rc == 0 || error("nk_mg_plan_periodic: no periodic plan (a used axis of fewer than 3 points)")
+    return [Tuple(ext[3l + 1:3l + 3]) for l in 0:nl[] - 1]
+end
 # the semicoarsened plan (host only): only the axes with c_a = |k_a| / h_a² >= threshold * max c are halved
 function mg_plan_semi(n::NTuple{3, Int64}, h::NTuple{3, Float64}; k::NTuple{3, Float64} = (1.0, 1.0, 1.0), threshold = 0.5,
                       max_levels = 0)
@@ -583,7 +596,7 @@ const _mg_cache = Dict{Any, HipMultigridPreconditioner}()
 # coarsening = :semi: the semicoarsened hierarchy, for grids whose spacings differ between the axes
 function hip_multigrid(J::Ariadne.JacobianOperator; spd = false, coarsening = :full, threshold = 0.5)
     pr = problem(J.f, J.u, J.p)
-    key = (J.u.ctx, size(J.u), pr.kind, pr.hx, pr.hy, pr.hz, coarsening, threshold)
+    key = (J.u.ctx, size(J.u), pr.kind, pr.hx, pr.hy, pr.hz, pr.bc, coarsening, threshold)
     haskey(_mg_cache, key) && return update!(mg_set_spd!(_mg_cache[key], spd), J)
     empty!(_mg_cache)
     return _mg_cache[key] = HipMultigridPreconditioner(J; spd = spd, coarsening = coarsening, threshold = threshold)

@@ -26,6 +26,15 @@ level-0 sweep (mg_sweep) and dot on a one-level hierarchy of every 2D grid, and 
 (mg_tail_dot) against mg_tail and dot on every 1D grid of at most 1024 points.  Writes mg_cg_solve.{txt,json}.
 
   python tools/mg_solve.py --algo cg [--grids 1000,10000,4096x4096] [--plain-steps 50]
+
+--workload heat2d | heat3d (with --scheme euler | midpoint | trapezoid, --bc periodic, --stiff = a Δt / h_x²): one stiff
+implicit heat step on a periodic grid (h = 1 / n per axis, u_n random), the Newton solve with N = multigrid(periodic=True)
+and without a preconditioner in one session, Newton / Krylov counts and wall time; then, per launch from the context's
+profile classes over --reps profiled V-cycles each, the transfers of the finest level pair of the periodic hierarchy
+(mg_restrict_per, mg_prolong_per) next to the Dirichlet hierarchy's (mg_restrict, mg_prolong) on the same extents, both
+cut to two levels so that each class holds that pair alone.  Writes mg_periodic_<workload>.{txt,json}.
+
+  python tools/mg_solve.py --workload heat2d --scheme trapezoid --bc periodic --stiff 1000 --grids 8192x8192 --out profiles/mg_periodic
 """
 import argparse
 import hashlib
@@ -270,6 +279,104 @@ def main_cg(args):
         f.write(text + "\n")
 
 
+THETA = {"euler": 1.0, "midpoint": 0.5, "trapezoid": 0.5}  # (midpoint: the default α = 1/2)
+HEAT_A = 0.01
+
+
+def heat_step(ctx, shape, scheme, stiff, un0, N, kw, memory, jv, max_niter=50):
+    """one implicit step from u_n with a Δt = stiff h_x²: the Newton solve, timed"""
+    d = len(shape)
+    h = [1.0 / n for n in shape]
+    dt = stiff * h[0] * h[0] / HEAT_A
+    f = getattr(ah, f"heat{d}d_{scheme}_")
+    un = ah.DeviceArray.from_numpy(un0, ctx=ctx)
+    p = (un, dt, un.zero(), (HEAT_A, *h, ah.bc_periodic_), 0.0)
+    u = un.copy()
+    ctx.sync()
+    t0 = time.perf_counter()
+    _, r = ah.newton_krylov_(f, u, p, N=N, memory=memory, krylov_kwargs=kw, jv=jv, tol_abs=6.0e-6, max_niter=max_niter)
+    ctx.sync()
+    return dict(solved=bool(r.solved), outer=r.stats.outer_iterations, inner=r.stats.inner_iterations, n_matvec=r.n_matvec,
+                n_res=r.stats.n_res, seconds=time.perf_counter() - t0)
+
+
+def transfer_profile(ctx, shape, k, periodic, reps):
+    """per-launch times of the finest pair's transfers on a two-level hierarchy: one profiled V-cycle per repetition"""
+    grid = ah.Grid.full(*shape)
+    h = [1.0 / n for n in shape]
+    mg = ah.MultigridPreconditioner.from_coefficients(grid, [k] * len(shape), -1.0, h=h, max_levels=2, periodic=periodic, ctx=ctx)
+    v = ah.DeviceArray.from_numpy(np.random.default_rng(1).standard_normal(tuple(reversed(shape))), ctx=ctx)
+    z = v.zero()
+    for _ in range(2):
+        mg.vcycle(v, z)
+    ctx.prof_enable(1)
+    per = {}
+    for _ in range(reps):
+        ctx.prof_reset()
+        mg.vcycle(v, z)
+        for name, e in ctx.prof_read().items():
+            if name.startswith(("mg_restrict", "mg_prolong", "mg_resid", "mg_sweep")) and e["timed"]:
+                per.setdefault(name, dict(us=[], model_bytes=e["bytes"] / e["timed"]))["us"].append(1e3 * e["ms"] / e["timed"])
+    ctx.prof_enable(0)
+    levels = mg.levels
+    mg.free()
+    return dict(levels=levels, kernels={n: dict(us_min=min(e["us"]), us_median=float(np.median(e["us"])), us_max=max(e["us"]),
+                                               model_bytes=e["model_bytes"],
+                                               fraction_of_peak_at_median=e["model_bytes"] / (np.median(e["us"]) * 1e-6) / PEAK)
+                                           for n, e in sorted(per.items())})
+
+
+def main_heat(args):
+    if args.bc != "periodic":
+        raise SystemExit("--workload heat2d / heat3d: only --bc periodic is implemented")
+    os.makedirs(args.out, exist_ok=True)
+    ctx = ah.Context(0)
+    ah.set_default_context(ctx)
+    d = 2 if args.workload == "heat2d" else 3
+    kw = dict(restart=True, itmax=args.itmax)
+    small = (96, 48) if d == 2 else (24, 12, 12)
+    un_small = np.random.default_rng(0).standard_normal(tuple(reversed(small)))
+    for N in (ah.multigrid(periodic=True), None):  # load every kernel before anything is timed
+        heat_step(ctx, small, args.scheme, args.stiff, un_small, N, kw, args.memory, args.jv)
+    out = dict(settings=dict(workload=args.workload, scheme=args.scheme, bc=args.bc, a_dt_over_hx2=args.stiff, krylov=kw,
+                             memory=args.memory, jv=args.jv, tol="6e-6 + 1e-6 ||F(u0)|| (solve's)", h="1 / n per axis"), grids=[])
+    lines = []
+    for g in args.grids.split(","):
+        shape = tuple(int(t) for t in g.split("x"))
+        assert len(shape) == d
+        un0 = np.random.default_rng(0).standard_normal(tuple(reversed(shape)))
+        row = dict(grid=list(shape), levels=ah.multigrid_plan(shape, periodic=True))
+        lines.append(f"== {args.workload} {args.scheme} periodic {g}, a dt / hx^2 = {args.stiff:g}, GMRES({args.memory}) restart "
+                     f"itmax {args.itmax}, {args.jv.upper()} Jv; {len(row['levels'])} levels")
+        fac = ah.multigrid(periodic=True)
+        row["multigrid"] = [heat_step(ctx, shape, args.scheme, args.stiff, un0, fac, kw, args.memory, args.jv) for _ in range(3)]
+        fac.free()
+        row["plain"] = [heat_step(ctx, shape, args.scheme, args.stiff, un0, None, kw, args.memory, args.jv, args.plain_steps)]
+        for tag in ("multigrid", "plain"):
+            for i, r in enumerate(row[tag]):
+                note = " (allocates the hierarchy)" if tag == "multigrid" and i == 0 else ""
+                if tag == "plain" and not r["solved"]:
+                    note = f" (stopped after {args.plain_steps} Newton steps of itmax {args.itmax}: not solved)"
+                lines.append(f"  {'N = multigrid(periodic)' if tag == 'multigrid' else 'plain':<24}: solved {r['solved']}  ||F|| {r['n_res']:.3e}  "
+                             f"Newton {r['outer']}  Krylov {r['inner']}  matvecs {r['n_matvec']}  {r['seconds']:.4f} s{note}")
+        theta = THETA[args.scheme]
+        k = theta * args.stiff / shape[0] ** 2
+        for tag, periodic in (("periodic", True), ("dirichlet", False), ("periodic_again", True), ("dirichlet_again", False)):
+            row["transfers_" + tag] = prof = transfer_profile(ctx, shape, k, periodic, args.reps)
+            lines.append(f"  two-level hierarchy {prof['levels']}, {tag}: per launch over {args.reps} profiled cycles (min / median / max us)")
+            for n, e in prof["kernels"].items():
+                lines.append(f"    {n:<20} {e['us_min']:9.1f} {e['us_median']:9.1f} {e['us_max']:9.1f}   model {e['model_bytes'] / 1e6:8.1f} MB  "
+                             f"{e['fraction_of_peak_at_median']:.2f} of 8 TB/s")
+        out["grids"].append(row)
+    text = "\n".join(lines)
+    print(text)
+    stem = os.path.join(args.out, f"mg_periodic_{args.workload}")
+    with open(stem + ".json", "w") as f:
+        json.dump(out, f, indent=1)
+    with open(stem + ".txt", "w") as f:
+        f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--algo", default="gmres", choices=["gmres", "cg"])
@@ -282,7 +389,16 @@ def main():
     ap.add_argument("--vcycle-only", action="store_true", help="--coarsening semi | both: the V-cycle profiles without the solves")
     ap.add_argument("--reps", type=int, default=5, help="--coarsening semi | both: timed solves per hierarchy")
     ap.add_argument("--tag", default="", help="--coarsening semi | both: suffix of the output files")
+    ap.add_argument("--workload", default="bratu", choices=["bratu", "heat2d", "heat3d"])
+    ap.add_argument("--scheme", default="trapezoid", choices=["euler", "midpoint", "trapezoid"])
+    ap.add_argument("--bc", default="zero", choices=["zero", "periodic"])
+    ap.add_argument("--stiff", type=float, default=1000.0, help="--workload heat*: a dt / h_x^2 of the step")
+    ap.add_argument("--itmax", type=int, default=300, help="--workload heat*: Krylov itmax per Newton step")
     args = ap.parse_args()
+    if args.workload != "bratu":
+        if not args.grids:
+            raise SystemExit("--workload heat*: give --grids")
+        return main_heat(args)
     if args.algo == "cg":
         return main_cg(args)
     args.grids = args.grids or "4096x4096,16384x2048"
